@@ -17,8 +17,11 @@ as one continuous pipeline of K x P proofs through spx_prove_many with B = --inf
 host worker threads, each with its own HIP stream and MSM workspace, so the sequential host Blake2s
 absorption of the matrices (~150 MB per proof, one pool of hashing threads per rank) overlaps other
 proofs' GPU work. value = constraints proved per second over the timed region (whole job).
-Beside it: single-proof latency (with and without the index-cached transcript), the index-cached
+A plain run does that and no more: set up, warm up, time the K steps, print the line (--dump-outputs
+DIR also writes the last timed step's proofs to DIR/proofs.npy). With --full, beside it:
+single-proof latency (with and without the index-cached transcript), the index-cached
 throughput, BASELINE config C2 (2^18, sumcheck-only, commitment stubbed) with its own HBM roofline,
+the rooflines, the N = 1 rehearsals of a G-GPU node, the committed records,
 and CPU baselines (test oracle: 1 core at --cpu-log-n, all cores at --cpu-all-log-n).
 
 N > 1: one process per GPU (torch.distributed.run). Default (--shard proof): every proof is split
@@ -26,10 +29,12 @@ over all ranks (hypercube blocks, per-round partials exchanged by
 shared-memory allgather, one communicator per proof in flight; --comm rccl: one RCCL communicator per rank, shared by the
 proofs in flight through the ordered exchange hub). Total work
 per step is fixed ("scaling": "strong"). --shard batch makes every rank prove its own P proofs
-("weak"); the other mode's value is reported beside the headline.
+("weak"); with --full the other mode's value, the proof groups and the other transport are reported
+beside the headline.
 
-Output: ONE JSON line on rank 0 (metric, value, roofline of the dominant kernel measured live with
-HIP events on the library's stream, cpu_baseline from the test oracle on a bounded sample).
+Output: ONE JSON line on rank 0 (metric, value, ms_per_step; with --full the roofline of the dominant
+kernel measured live with HIP events on the library's stream, cpu_baseline from the test oracle on a
+bounded sample).
 """
 import argparse
 import ctypes
@@ -657,6 +662,27 @@ def run_rehearsal(args, log_n, log_v, P):
     return rehearsal
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, proofs):
+    """--dump-outputs: the proofs of the last timed step, in the order prove_many returned them, as
+    `path`/proofs.npy: float32 [proofs, proof bytes], one byte value (0..255) per element. The witnesses
+    and every seed are fixed by the arguments, so two builds can be compared proof for proof. Beyond
+    64 MB a fixed seeded sample of the proofs (rows in ascending order) is written instead."""
+    import numpy as np
+
+    size = len(proofs[0])
+    assert all(len(p) == size for p in proofs), "proofs of one step differ in length"
+    rows = max(1, DUMP_MAX_BYTES // (4 * size))
+    if len(proofs) > rows:
+        keep = np.sort(np.random.default_rng(0x5EED).choice(len(proofs), rows, replace=False))
+        proofs = [proofs[i] for i in keep]
+    a = np.frombuffer(b"".join(proofs), dtype=np.uint8).reshape(len(proofs), size).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "proofs.npy"), a)
+
+
 T_START = time.perf_counter()
 PHASE = ["start"]
 
@@ -726,7 +752,20 @@ def main():
                     "8 x G (at most 64) for proofs sharded over G >= 4 ranks (inflight_for)")
     ap.add_argument("--proofs-per-step", type=int, default=64,
                     help="proofs per step (a multiple of --inflight); the K steps run as one pipeline of K x P proofs")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: single-proof latency and per-kernel statistics with one proof at a time, the "
+                    "roofline, the index-cached transcript runs, the C2 line, the CPU baselines and the parity against the "
+                    "oracle, the committed records, the N = 1 rehearsals, and for N > 1 the other shard mode, the proof groups "
+                    "and the second transport (each still subject to its own --no-* switch). Without it the run sets up, "
+                    "warms up, times the --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proofs of the last timed step (what prove_many returned for its "
+                    "--proofs-per-step witnesses, in order) as DIR/proofs.npy: float32 [proofs, proof bytes], one byte value "
+                    "per element (a fixed seeded sample of the proofs where they would exceed 64 MB)")
     args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline alone
+        args.rehearse = args.groups = ""
+        args.no_cpu = args.no_c2 = args.no_cached = args.no_other = args.one_comm = True
     heartbeat()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the driver's `python bench.py --gpus N`: this process becomes the launcher of N ranks
@@ -900,18 +939,22 @@ def main():
         stats = kernel_stats(spx, L, hctx, args.steps * (P // len(hctxs)))  # ctx 0 proves P / B proofs per step
         spx._check(L.spx_kernel_stats_enable(hctx.h, 0))
     ref = check_batch(proofs)
-    # ---- single-proof latency (one proof at a time), with and without the index-cached transcript.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proofs[-P:])
+    # ---- --full: single-proof latency (one proof at a time), with and without the index-cached transcript.
     # Kernel durations with one proof at a time (no other proof sharing the GPU) come from the
     # per-proof-absorbed loop: the same launch mix as the batched proofs (level 0 as its own MSM)
-    if not args.no_stats:
-        spx._check(L.spx_kernel_stats_enable(hctx.h, 1))
-    p1, elapsed_single = timed(single_fn(hctx, hpk))
-    assert p1 == ref[0], "single proof differs from the batched one"
-    phases = hctx.last_timings()
-    alone = {}
-    if not args.no_stats:
-        alone = kernel_stats(spx, L, hctx, args.steps)
-        spx._check(L.spx_kernel_stats_enable(hctx.h, 0))
+    elapsed_single = None
+    phases, alone = {}, {}
+    if args.full:
+        if not args.no_stats:
+            spx._check(L.spx_kernel_stats_enable(hctx.h, 1))
+        p1, elapsed_single = timed(single_fn(hctx, hpk))
+        assert p1 == ref[0], "single proof differs from the batched one"
+        phases = hctx.last_timings()
+        if not args.no_stats:
+            alone = kernel_stats(spx, L, hctx, args.steps)
+            spx._check(L.spx_kernel_stats_enable(hctx.h, 0))
     elapsed_single_c = elapsed_cached = None
     phases_c = {}
     if not args.no_cached:
@@ -968,7 +1011,7 @@ def main():
 
     ms = elapsed / args.steps * 1e3  # per step (P proofs)
     ms_c = elapsed_cached / args.steps * 1e3 if elapsed_cached else 0.0
-    ms_1 = elapsed_single / args.steps * 1e3
+    ms_1 = elapsed_single / args.steps * 1e3 if elapsed_single else 0.0
     ms_1c = elapsed_single_c / args.steps * 1e3 if elapsed_single_c else 0.0
     ms_o = ms_o1 = None
     ms_g = {}
@@ -1066,8 +1109,9 @@ def main():
                 "comm": args.comm if sctxs else None,
                 "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "0")) or None,  # hardware queues per process
             },
-            "ms_per_proof_single": round(ms_1, 3),
-            "value_single_proof": round(n / (ms_1 / 1e3), 1),
+            "full": args.full,
+            "ms_per_proof_single": round(ms_1, 3) if ms_1 else None,
+            "value_single_proof": round(n / (ms_1 / 1e3), 1) if ms_1 else None,
             "ms_per_proof_single_cached_transcript": round(ms_1c, 3) if ms_1c else None,
             "value_single_proof_cached_transcript": round(n / (ms_1c / 1e3), 1) if ms_1c else None,
             "value_index_cached_transcript": round(jobs * n / (ms_c / 1e3), 1) if ms_c else None,
@@ -1095,13 +1139,13 @@ def main():
         # (the pool's own clock over the timed region: multi-buffer lanes hash several proofs per job)
         hash_s = phases.get("transcript_matrices", 0.0) / 1e6
         pool_s, pool_n = hs1[0] - hs0[0], hs1[1] - hs0[1]
-        if world == 1 and log_n == 20 and not stub and args.kind == 3:
+        if args.full and world == 1 and log_n == 20 and not stub and args.kind == 3:
             # the headline's baseline at the metric's own size: one core, 2^20 (committed record)
             c1 = committed_record(CPU1_2_20_FILE)
             if c1:  # the cross-check of the in-run 1-core 2^20 leg (run last, make_out)
                 c1["gpu_value_over_it"] = round(out["value"] / c1["value"], 1)
                 out["cpu_baseline_1core_2_20_record"] = c1
-        c5 = committed_record(C5_FILE)
+        c5 = committed_record(C5_FILE) if args.full else None
         if c5 and not stub:
             out["c5_parity_2_24"] = {"equal": c5.get("equal"), "ranks": c5.get("ranks"), "proof_bytes": c5.get("proof_bytes"),
                                      "oracle_cores": c5.get("oracle_threads"), "oracle_s": c5.get("oracle_s"),
@@ -1113,7 +1157,7 @@ def main():
         out["host"] = {"cpu_count": os.cpu_count(), "cores_used": host_cores(),
                        "hashing_lanes": hs1[2],
                        "hashing_core_s_per_proof": round(pool_s / pool_n, 4) if pool_n else None,
-                       "hashing_s_single_proof_scalar": round(hash_s, 4),
+                       "hashing_s_single_proof_scalar": round(hash_s, 4) if phases else None,
                        "hashing_cores_busy": round(pool_s / elapsed, 2) if pool_n else 0.0,
                        # summed over the proof workers: time a proof waited for its absorption
                        "hashing_wait_ms_per_proof": round((hs1[3] - hs0[3]) / pool_n * 1e3, 2) if pool_n else None,

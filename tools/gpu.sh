@@ -5,7 +5,7 @@
 # STEP is one of
 #   tests[=PYTEST_ARGS]   pytest -m gpu (default: the whole tests/ tree)           -> TAG_tests.log
 #   smoke                 __graft_entry__.smoke()                                    -> TAG_smoke.log
-#   bench[=ARGS]          python bench.py ARGS (default: the driver's no-flag run)   -> TAG_bench.json
+#   bench[=ARGS]          python bench.py ARGS (default: --full, every measurement) -> TAG_bench.json
 #   samegpu=N[,ARGS]      bench.py --gpus N with every rank on GPU 0 (SPX_BENCH_SAME_GPU=1)
 #                                                                                    -> TAG_samegpuN.json
 #   profile               tools/profile_gpu.sh TAG (rocprofv3 traces + PMC passes)
@@ -28,11 +28,11 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/${TAG}_smoke.log" 2>&1 || exit $? ;;
     bench)
       # shellcheck disable=SC2086
-      timeout -k 10 900 python -u bench.py $arg > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" || exit $? ;;
+      timeout -k 10 900 python -u bench.py ${arg:---full} > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" || exit $? ;;
     samegpu)
       n="${arg%%,*}"; extra=""; [[ "$arg" == *,* ]] && extra="${arg#*,}"
       # shellcheck disable=SC2086
-      SPX_BENCH_SAME_GPU=1 timeout -k 10 700 python -u bench.py --gpus "$n" $extra \
+      SPX_BENCH_SAME_GPU=1 timeout -k 10 700 python -u bench.py --full --gpus "$n" $extra \
         > "$O/${TAG}_samegpu${n}.json" 2> "$O/${TAG}_samegpu${n}.err" || exit $? ;;
     profile)
       timeout -k 10 1100 bash tools/profile_gpu.sh "$TAG" || exit $? ;;

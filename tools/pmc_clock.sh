@@ -10,7 +10,7 @@ RAW="/tmp/pc_$TAG"
 mkdir -p "$OUT" "$RAW"
 export TMPDIR=/tmp
 cd /tmp
-B1="--steps 1 --warmup 1 --no-cpu --no-c2 --no-cached --inflight 1 --proofs-per-step 4 --rehearse= --no-stats"
+B1="--full --steps 1 --warmup 1 --no-cpu --no-c2 --no-cached --inflight 1 --proofs-per-step 4 --rehearse= --no-stats"
 # shellcheck disable=SC2086
 timeout -s KILL 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_BUSY_CYCLES --kernel-trace -d "$RAW/pmc" -o run \
     --output-format csv -- python3 "$ROOT/bench.py" $B1 > /dev/null 2> "$OUT/${TAG}_clock.err"

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=16
 cd /tmp
 timeout -s KILL 60 rocprofv3 -L > "$OUT/avail.txt" 2>&1 || true
-B1="--steps 1 --warmup 1 --no-cpu --no-c2 --no-cached --inflight 1 --proofs-per-step 4 --no-stats"
+B1="--full --steps 1 --warmup 1 --no-cpu --no-c2 --no-cached --inflight 1 --proofs-per-step 4 --no-stats"
 pass() {  # $1 = name, rest = counters
   local name="$1"; shift
   for c in "$@"; do grep -qw "$c" "$OUT/avail.txt" || { echo "skip $name: $c not listed" >&2; return 0; }; done

@@ -22,12 +22,12 @@ export GPU_MAX_HW_QUEUES="${PROF_HW_QUEUES:-16}"
 cd /tmp
 # one proof in flight, no index-cached runs: every G2 launch of the process is one of the three per
 # proof that bench.py's "alone" statistics time (level 0, the two opening batches)
-B1="--steps 1 --warmup 1 --no-cpu --no-c2 --no-cached --inflight 1 --proofs-per-step 4 --rehearse="
+B1="--full --steps 1 --warmup 1 --no-cpu --no-c2 --no-cached --inflight 1 --proofs-per-step 4 --rehearse="
 # BASELINE C2 (2^18, commitment stubbed): its own FETCH / WRITE passes for the c2 roofline's traffic
-C2="--config c2 --steps 1 --warmup 1 --no-cpu --no-cached --inflight 1 --proofs-per-step 4 --rehearse="
+C2="--full --config c2 --steps 1 --warmup 1 --no-cpu --no-cached --inflight 1 --proofs-per-step 4 --rehearse="
 if [ -z "$PROF_SKIP_TRACE" ]; then
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$RAW/trace" -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu --no-c2 --rehearse= > "$OUT/bench_traced.json" 2> "$OUT/trace.err"
+    python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu --no-c2 --rehearse= > "$OUT/bench_traced.json" 2> "$OUT/trace.err"
 echo "trace done" >&2
 find "$RAW/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$RAW/trace1" -o run --output-format csv -- \

@@ -13,7 +13,7 @@ mkdir -p "$OUT" "$RAW"
 export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=16
 cd /tmp
-B1="--steps 1 --warmup 1 --no-cpu --no-c2 --no-cached --inflight 1 --proofs-per-step 4 --rehearse="
+B1="--full --steps 1 --warmup 1 --no-cpu --no-c2 --no-cached --inflight 1 --proofs-per-step 4 --rehearse="
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$RAW/trace" -o run --output-format csv -- \
     python3 "$ROOT/bench.py" $B1 > "$OUT/${TAG}_bench_traced.json" 2> "$OUT/${TAG}_trace.err"
 find "$RAW/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/${TAG}_kernel_stats.csv" \;
