@@ -131,6 +131,13 @@ int spx_ctx_set_comm_rehearsal(spx_ctx *ctx, int rank, int world);
  * Every rank of a proof-sharded prove must use the same mode (checked on the context's first sharded
  * proof: SPX_INVALID_ARGUMENT otherwise). */
 int spx_ctx_set_lvl0_batch(spx_ctx *ctx, int mode);
+/* Hot-bucket reduction of this context's MSMs (no effect on the proof bytes): a bucket that the
+ * planned partial levels leave with more than 4 partials (skewed scalars: a 0 / 1 witness sends every
+ * 1 to one bucket) is reduced by a parallel tree before the bucket weighting. 1 = on (the default),
+ * 0 = off (such buckets are still listed and counted, then added serially by the weighting leaf: A/B),
+ * -1 = the process default (SPX_MSM_HOT=0 -> 0, else 1). Each rank of a proof-sharded prove may choose
+ * its own. SPX_INVALID_ARGUMENT while the context is in use. */
+int spx_ctx_set_msm_hot(spx_ctx *ctx, int mode);
 /* one allgather on the context's communicator (whatever its transport): every rank passes `bytes`,
  * recv receives world * bytes in rank order. For transport tests. */
 int spx_ctx_comm_allgather(spx_ctx *ctx, const void *send, void *recv, size_t bytes);
@@ -303,6 +310,13 @@ int spx_kernel_ops(spx_ctx *ctx, int id, double *ops);
  * compacted keys overflowed their planned capacity (scalars crowding one rank's buckets); a
  * diagnostic: the results are exact either way */
 int spx_msm_reruns(spx_ctx *ctx, uint64_t *reruns);
+
+/* Scalar skew met by this context's MSMs, cumulative: out[0] MSM batches run, out[1] batches with at
+ * least one hot bucket (see spx_ctx_set_msm_hot), out[2] hot buckets reduced, out[3] the largest
+ * number of partials the weighting leaf added for one bucket (<= 4 with the reduction on). Read from
+ * the status words that come back with each batch's results: no extra synchronisation. A diagnostic:
+ * the results are exact either way. */
+int spx_msm_skew_stats(spx_ctx *ctx, uint64_t out[4]);
 
 /* ---- kernel-level entry points (parity tests) ---- */
 int spx_sum_over_y(spx_ctx *ctx, const spx_csr *m, const uint8_t *z, uint8_t *out);

@@ -84,6 +84,7 @@ EXPORTED = [
     "spx_ctx_set_comm_group",
     "spx_ctx_set_comm_rehearsal",
     "spx_ctx_set_lvl0_batch",
+    "spx_ctx_set_msm_hot",
     "spx_comm_hub_create_rccl",
     "spx_comm_hub_create_shm",
     "spx_comm_hub_create_group",
@@ -94,6 +95,7 @@ EXPORTED = [
     "spx_comm_hub_destroy",
     "spx_ctx_comm_allgather",
     "spx_msm_reruns",
+    "spx_msm_skew_stats",
     "spx_ctx_mem_info",
     "spx_ctx_set_sync_poll",
     "spx_ctx_set_group",
@@ -182,6 +184,9 @@ def lib():
         L.spx_ctx_mem_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "spx_ctx_set_lvl0_batch"):  # A/B builds may predate it
         L.spx_ctx_set_lvl0_batch.argtypes = [vp, ctypes.c_int]
+    if hasattr(L, "spx_ctx_set_msm_hot") or not os.environ.get("SPX_LIB_PATH"):
+        L.spx_ctx_set_msm_hot.argtypes = [vp, ctypes.c_int]
+        L.spx_msm_skew_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "spx_comm_hub_create_rccl") or not os.environ.get("SPX_LIB_PATH"):  # A/B builds may predate the hub
         L.spx_comm_hub_create_rccl.argtypes = [u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
         L.spx_comm_hub_create_shm.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
@@ -344,6 +349,19 @@ class Context:
         """where the shared level-0 opening MSM runs: 1 inside the first opening's batch, 0 beside the
         commitment, -1 the process default (SPX_LVL0); the same on every rank of a sharded prove"""
         _check(lib().spx_ctx_set_lvl0_batch(self.h, int(mode)))
+
+    def set_msm_hot(self, mode):
+        """hot-bucket reduction of this context's MSMs (skewed scalars, e.g. a 0 / 1 witness): 1 on (the
+        default), 0 off (listed and counted only: A/B), -1 the process default (SPX_MSM_HOT); no effect
+        on the proof bytes (spx_ctx_set_msm_hot)"""
+        _check(lib().spx_ctx_set_msm_hot(self.h, int(mode)))
+
+    def msm_skew_stats(self):
+        """(MSM batches run, batches with a hot bucket, hot buckets reduced, most partials the weighting
+        leaf added for one bucket), cumulative (spx_msm_skew_stats)"""
+        v = (ctypes.c_uint64 * 4)()
+        _check(lib().spx_msm_skew_stats(self.h, v))
+        return tuple(int(x) for x in v)
 
     def comm_allgather(self, data, world):
         """one allgather of `data` on this context's communicator -> list of world byte strings"""
@@ -561,7 +579,9 @@ class PublicParameter:
 
     def __del__(self):
         try:
-            if self.h:
+            # (a handle outliving its context is dropped, not freed: the library's free reads the
+            # context, and the garbage collector may finalise the context first)
+            if self.h and self.ctx.h:
                 lib().spx_pp_free(self.h)
         except Exception:
             pass
@@ -575,7 +595,9 @@ class IndexPK:
 
     def __del__(self):
         try:
-            if self.h:
+            # (a handle outliving its context is dropped, not freed: the library's free reads the
+            # context, and the garbage collector may finalise the context first)
+            if self.h and self.ctx.h:
                 lib().spx_index_free(self.h)
         except Exception:
             pass
@@ -592,7 +614,9 @@ class Witness:
 
     def __del__(self):
         try:
-            if self.h:
+            # (a handle outliving its context is dropped, not freed: the library's free reads the
+            # context, and the garbage collector may finalise the context first)
+            if self.h and self.ctx.h:
                 lib().spx_witness_free(self.h)
         except Exception:
             pass

@@ -270,6 +270,15 @@ int spx_ctx_set_lvl0_batch(spx_ctx* ctx, int mode) {
     });
 }
 
+int spx_ctx_set_msm_hot(spx_ctx* ctx, int mode) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (mode < -1 || mode > 1) spx::invalid("MSM hot-bucket mode must be -1, 0 or 1");
+        if (ctx->c->in_use.load()) spx::invalid("context in use by a prove or session");
+        ctx->c->set_msm_hot(mode);
+    });
+}
+
 int spx_ctx_comm_allgather(spx_ctx* ctx, const void* send, void* recv, size_t bytes) {
     return guard([&] {
         set_dev(ctx);
@@ -686,6 +695,15 @@ int spx_msm_reruns(spx_ctx* ctx, uint64_t* reruns) {
     return guard([&] {
         if (!ctx || !reruns) spx::invalid("null argument");
         *reruns = ctx->c->msm_reruns.load();
+    });
+}
+int spx_msm_skew_stats(spx_ctx* ctx, uint64_t out[4]) {
+    return guard([&] {
+        if (!ctx || !out) spx::invalid("null argument");
+        out[0] = ctx->c->skew_batches.load();
+        out[1] = ctx->c->skew_hot_batches.load();
+        out[2] = ctx->c->skew_reduced.load();
+        out[3] = ctx->c->skew_leaf_max.load();
     });
 }
 int spx_sum_over_y(spx_ctx* ctx, const spx_csr* m, const uint8_t* z, uint8_t* out) {

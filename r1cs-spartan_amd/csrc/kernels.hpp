@@ -280,7 +280,13 @@ struct MsmShard {
     bool dense = false;  // world > 1: one key slot per (scalar, window), as at world 1 (never overflows)
 };
 static constexpr uint32_t kMsmOverflow = 1;  // status bit: compacted keys exceeded their capacity
+// the other three status words: hot buckets listed / reduced, and the largest number of partials the
+// weighting leaf added for one bucket where that exceeds 1 (0: no bucket had more than one)
+enum { kMsmStHot = 1, kMsmStReduced = 2, kMsmStLeafMax = 3 };
 
+// buckets one batch may hold: the sort's 2048 bins of <= 2^8 buckets (msm_common.hip); prover.hpp ties
+// kMaxLogN to it
+static constexpr uint64_t kMsmMaxBuckets = 2048ull << 8;
 struct MsmWorkspace;  // opaque, owned by the host side (msm.hip)
 MsmWorkspace* msm_ws_create();
 void msm_ws_destroy(MsmWorkspace* ws);
@@ -288,9 +294,13 @@ void msm_ws_destroy(MsmWorkspace* ws);
 void msm_ws_staging_reset(MsmWorkspace* ws);
 // a batch of this workspace reported kMsmOverflow: raise its compacted-key capacity for later batches
 void msm_ws_note_overflow(MsmWorkspace* ws);
+// hot-bucket reduction of this workspace's batches: on (the default), or off (listed and counted, then
+// left to the weighting leaf: A/B); msm_hot_default: SPX_MSM_HOT=0 -> off, else on
+void msm_ws_set_hot(MsmWorkspace* ws, bool on);
+bool msm_hot_default();
 
 // bytes of a batch's output buffer: one XYZZ point per instance (G1: 4 x 48 B, G2: 4 x 96 B,
-// Montgomery limbs; infinity = all zero), then a 16-byte status word (kMsmOverflow)
+// Montgomery limbs; infinity = all zero), then a 16-byte status word (kMsmOverflow, kMsmSt*)
 inline size_t msm_out_bytes(bool g2, int ninst) { return (size_t)ninst * (g2 ? 4 * 96 : 4 * 48) + 16; }
 // Enqueues a batch of MSMs on `s` without any host synchronisation. With world > 1 and !dense the
 // keys are compacted into a capacity planned from the expected bucket occupancy; if the status word

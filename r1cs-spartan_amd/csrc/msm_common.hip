@@ -134,6 +134,7 @@ static constexpr uint32_t kMaxBins = 2048;    // K1 / K3: LDS words per bin
 static constexpr uint32_t kStagePairs = (uint32_t)kTileThreads * 16;  // K3: one iteration's pairs (<= 16 per scalar)
 static constexpr uint32_t kBinStage = 36864;  // K4: a bin's references ordered in LDS (144 KB); larger bins write directly
 static constexpr int kMaxLev = 8;             // XYZZ partial levels the sort prepares offsets for
+static_assert(((uint64_t)kMaxBins << 8) == kMsmMaxBuckets, "kMsmMaxBuckets (kernels.hpp): kMaxBins bins of 2^8 buckets");
 typedef __attribute__((address_space(1))) unsigned int gu32;
 
 struct SortGeom {
@@ -181,6 +182,24 @@ DEV bool handoff_last(uint32_t* __restrict__ ticket, uint32_t ntickets, bool* fl
 DEV void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store((gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 DEV uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load((const gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// ++ctr[k] on an LDS counter array, aggregated over the wave; returns the value before the caller's
+// own increment (its rank under the counter). Skewed scalars (0 / 1 witnesses) send every lane of a
+// wave to one counter, where 64 LDS atomics serialise: the calling lanes that share the first
+// calling lane's key are balloted, that lane adds their number in one atomic and each takes its rank
+// below it from mbcnt; the other lanes issue their ordinary atomics in the same instruction. A wave
+// of distinct keys costs the compare and the ballot on top of the atomic it issued before. Callable
+// under divergence (the calling lanes are the exec mask).
+DEV uint32_t lds_inc(uint32_t* ctr, uint32_t k) {
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane(k);
+    const bool same = k == k0;
+    const uint64_t m = __ballot(same);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    uint32_t old = 0;
+    if (!same || rank == 0) old = atomicAdd(&ctr[k], same ? (uint32_t)__popcll(m) : 1u);
+    const uint32_t lead = __builtin_amdgcn_readfirstlane(old);  // the first calling lane is the leader
+    return same ? lead + rank : old;
+}
+
 // K1 runs kSub workgroups of kCountThreads per tile (more, smaller workgroups than K3's: K1 is the
 // digit extraction alone); sub-unit u counts scalars [u, u + 1) x kCountThreads x spt, so the kSub
 // sub-units of tile t cover exactly its scalars, and column kSub t of a scanned row is the tile's prefix
@@ -200,7 +219,7 @@ __global__ __launch_bounds__(kCountThreads) void k_sort_count(const MsmInst* __r
         const uint64_t gi = t0 + (uint64_t)k * kCountThreads;
         if (gi >= g.tot_sc) break;
         Keys16 kk;
-        auto add = [&](uint32_t key, uint32_t) { atomicAdd(&h[key >> g.sb], 1u); };
+        auto add = [&](uint32_t key, uint32_t) { lds_inc(h, key >> g.sb); };
         if (scalar_keys(insts, prefix, nact, scalars, gi, kk, add)) {
 #pragma unroll
             for (int w = 0; w < 16; ++w)
@@ -282,14 +301,17 @@ __global__ __launch_bounds__(kTileThreads) void k_sort_scatter(const MsmInst* __
         uint32_t rk[16];
         if (gi < g.tot_sc) {
             auto direct = [&](uint32_t key, uint32_t ref) {
-                const uint32_t q = atomicAdd(&L.pos[key >> g.sb], 1u);
+                const uint32_t q = lds_inc(L.pos, key >> g.sb);
                 sref[q] = ref;
                 sfine[q] = (uint8_t)(key & fmask);
             };
             fast = scalar_keys(insts, prefix, nact, scalars, gi, kk, direct);
             if (fast) {
 #pragma unroll
-                for (int w = 0; w < 16; ++w) rk[w] = kk.key[w] != ~0u ? atomicAdd(&L.lst[kk.key[w] >> g.sb], 1u) : 0u;
+                for (int w = 0; w < 16; ++w) {
+                    rk[w] = 0u;
+                    if (kk.key[w] != ~0u) rk[w] = lds_inc(L.lst, kk.key[w] >> g.sb);
+                }
             }
         }
         __syncthreads();
@@ -352,14 +374,17 @@ __global__ __launch_bounds__(kDirectThreads) void k_sort_scatter_direct(const Ms
         if (gi >= g.tot_sc) break;
         Keys16 kk;
         auto put = [&](uint32_t key, uint32_t ref) {
-            const uint32_t q = atomicAdd(&pos[key >> g.sb], 1u);
+            const uint32_t q = lds_inc(pos, key >> g.sb);
             sref[q] = ref;
             sfine[q] = (uint8_t)(key & fmask);
         };
         if (scalar_keys(insts, prefix, nact, scalars, gi, kk, put)) {
             uint32_t q[16];
 #pragma unroll
-            for (int w = 0; w < 16; ++w) q[w] = kk.key[w] != ~0u ? atomicAdd(&pos[kk.key[w] >> g.sb], 1u) : 0u;
+            for (int w = 0; w < 16; ++w) {
+                q[w] = 0u;
+                if (kk.key[w] != ~0u) q[w] = lds_inc(pos, kk.key[w] >> g.sb);
+            }
 #pragma unroll
             for (int w = 0; w < 16; ++w)
                 if (kk.key[w] != ~0u) {
@@ -374,7 +399,9 @@ __global__ __launch_bounds__(kDirectThreads) void k_sort_scatter_direct(const Ms
 // seg1-reference thread ranges [o, o + c) meets; XYZZ level l: ceil(previous / kSeg)) scanned inside
 // the bin into lev[l], the bin's totals handed to the last block, which scans them into
 // binpfx[l][bin]; then the bin's references ordered by bucket in LDS and written back contiguously
-// (a bin larger than the staging: each reference written to its slot directly)
+// (a bin larger than the staging: each reference written to its slot directly). A bucket that the
+// planned levels leave more than kSeg partials (v_nlev > kSeg) is hot: it is appended to the batch's
+// hot list, whose counter is status word kMsmStHot (zeroed by K1), for k_accum_hot (msm_impl.hpp).
 template <int NT, uint32_t STAGE>
 struct BinLds {
     uint32_t out[STAGE ? STAGE : 1];
@@ -386,11 +413,12 @@ struct LevPtrs {
 // NT threads (>= 256: one per in-bin bucket); STAGE: LDS staging capacity (0: every reference written directly)
 template <int NT, uint32_t STAGE>
 __global__ __launch_bounds__(NT) void k_sort_bins(SortGeom g, const uint32_t* __restrict__ binbase,
-                                                            const uint32_t* __restrict__ st, const uint32_t* __restrict__ sref,
+                                                            uint32_t* __restrict__ st, const uint32_t* __restrict__ sref,
                                                             const uint8_t* __restrict__ sfine, uint32_t* __restrict__ offs,
                                                             uint32_t* __restrict__ refs, uint32_t seg1, int nlev, LevPtrs lev,
                                                             uint32_t* __restrict__ binsum, uint32_t* __restrict__ binpfx,
-                                                            uint32_t* __restrict__ ticket) {
+                                                            uint32_t* __restrict__ ticket, uint32_t* __restrict__ hot,
+                                                            uint32_t hot_cap) {
     __shared__ BinLds<NT, STAGE> L;
     __shared__ bool last;
     const uint32_t bin = blockIdx.x, f = threadIdx.x;
@@ -406,7 +434,7 @@ __global__ __launch_bounds__(NT) void k_sort_bins(SortGeom g, const uint32_t* __
         const uint32_t w4 = *(const uint32_t*)(sfine + a0 + 4 * q);
 #pragma unroll
         for (uint32_t e = 0; e < 4; ++e)
-            if (4 * q + e - head < n) atomicAdd(&L.h[(w4 >> (8 * e)) & 0xFFu], 1u);
+            if (4 * q + e - head < n) lds_inc(L.h, (w4 >> (8 * e)) & 0xFFu);
     }
     __syncthreads();
     const uint32_t c = f < nbk ? L.h[f] : 0u;
@@ -422,6 +450,10 @@ __global__ __launch_bounds__(NT) void k_sort_bins(SortGeom g, const uint32_t* __
         if (f < nbk) lev.p[l][b0 + f] = e;
         if (f == 0) st_agent(binsum + (size_t)l * (g.nbin + 1) + bin, agg);
     }
+    if (v > kSeg) {  // hot (the capacity is an upper bound of their number: msm_hot_cap)
+        const uint32_t i = atomicAdd(&st[kMsmStHot], 1u);
+        if (i < hot_cap) hot[i] = b0 + f;
+    }
     const bool staged = n <= STAGE;
     if (f < 256) L.h[f] = staged ? lo : o;  // each bucket's next slot (in LDS / in refs)
     __syncthreads();
@@ -432,7 +464,7 @@ __global__ __launch_bounds__(NT) void k_sort_bins(SortGeom g, const uint32_t* __
 #pragma unroll
         for (uint32_t e = 0; e < 4; ++e)
             if (4 * q + e - head < n) {
-                const uint32_t slot = atomicAdd(&L.h[(w4 >> (8 * e)) & 0xFFu], 1u);
+                const uint32_t slot = lds_inc(L.h, (w4 >> (8 * e)) & 0xFFu);
                 if (staged)
                     L.out[slot] = rr[e];
                 else
@@ -493,13 +525,35 @@ uint32_t seg1_fit(uint32_t seg1, uint64_t refs, int waves_per_simd, int lanes_pe
     return (uint32_t)std::min<uint64_t>(seg1, std::max<uint64_t>(fit, std::min<uint32_t>(seg1, 8)));
 }
 
-MsmWorkspace* msm_ws_create() { return new MsmWorkspace(); }
+MsmWorkspace* msm_ws_create() {
+    auto* ws = new MsmWorkspace();
+    ws->hot_on = msm_hot_default();
+    return ws;
+}
 void msm_ws_destroy(MsmWorkspace* ws) { delete ws; }
 void msm_ws_staging_reset(MsmWorkspace* ws) {
     if (ws) ws->pin.reset();
 }
 void msm_ws_note_overflow(MsmWorkspace* ws) {
     if (ws) ws->cap_scale = std::min(ws->cap_scale * 1.5, 64.0);
+}
+void msm_ws_set_hot(MsmWorkspace* ws, bool on) {
+    if (ws) ws->hot_on = on;
+}
+bool msm_hot_default() {  // SPX_MSM_HOT=0 (A/B): hot buckets are left to the weighting leaf
+    static const bool v = [] {
+        const char* e = getenv("SPX_MSM_HOT");
+        return !(e && atoi(e) == 0 && *e);
+    }();
+    return v;
+}
+uint32_t msm_hot_cap(uint64_t tot_refs, uint32_t seg1, int nlev) {
+    uint64_t per = 1;  // kSeg^(nlev + 1) - 1 full runs of seg1 references at least in a hot bucket
+    for (int l = 0; l <= nlev; ++l) per *= kSeg;
+    const uint64_t cap = tot_refs / ((per - 1) * std::max<uint32_t>(seg1, 1)) + 1;
+    // it holds every bucket that can be hot: not below the count of buckets past kSeg seg1 kSeg^nlev references
+    if (cap < tot_refs / (per * std::max<uint32_t>(seg1, 1)) + 1) throw std::runtime_error("MSM: hot-bucket list capacity");
+    return (uint32_t)std::min<uint64_t>(cap, 0xffffffffu);
 }
 
 static double msm_cap_env() {  // SPX_MSM_CAP_SCALE (tests): scales the compacted-key capacity, e.g. 0.5 forces overflow
@@ -686,6 +740,8 @@ MsmSorted msm_sort(MsmWorkspace* ws, const MsmPlan& p, const Fr* scalars, void* 
     }
     LevPtrs lp{};
     for (int l = 0; l <= nlev; ++l) lp.p[l] = lv + (size_t)l * (nb + 1);
+    o.hot_cap = msm_hot_cap(p.tot_refs, seg1, nlev);
+    o.hot = (uint32_t*)ws->hot.ensure(4 * (size_t)o.hot_cap);
     const int nact = (int)p.insts.size();
     kp_begin(KP_SORT, s);
     hipLaunchKernelGGL(k_sort_count, dim3(g.ntile * g.sub), dim3(kCountThreads), 0, s, p.d_insts, p.d_prefix, nact, scalars, g,
@@ -697,14 +753,14 @@ MsmSorted msm_sort(MsmWorkspace* ws, const MsmPlan& p, const Fr* scalars, void* 
         hipLaunchKernelGGL(k_sort_scatter, dim3(g.ntile), dim3(kTileThreads), 0, s, p.d_insts, p.d_prefix, nact, scalars, g, cnt,
                            binbase, st, sref, sfine);
         hipLaunchKernelGGL((k_sort_bins<kBinThreads, kBinStage>), dim3(g.nbin), dim3(kBinThreads), 0, s, g, binbase, st, sref,
-                           sfine, o.offs, o.refs, seg1, nlev, lp, binsum, binpfx, tk + 16);
+                           sfine, o.offs, o.refs, seg1, nlev, lp, binsum, binpfx, tk + 16, o.hot, o.hot_cap);
     } else {
         hipLaunchKernelGGL(k_sort_scan<kDirectThreads>, dim3(g.nbin), dim3(kDirectThreads), 0, s, cnt, g, bintot, binbase, tk,
                            cap32, st, o.offs + nb);
         hipLaunchKernelGGL(k_sort_scatter_direct, dim3(g.ntile), dim3(kDirectThreads), 0, s, p.d_insts, p.d_prefix, nact, scalars,
                            g, cnt, binbase, st, sref, sfine);
         hipLaunchKernelGGL((k_sort_bins<kDirectThreads, 0>), dim3(g.nbin), dim3(kDirectThreads), 0, s, g, binbase, st, sref,
-                           sfine, o.offs, o.refs, seg1, nlev, lp, binsum, binpfx, tk + 16);
+                           sfine, o.offs, o.refs, seg1, nlev, lp, binsum, binpfx, tk + 16, o.hot, o.hot_cap);
     }
     const uint64_t nfin = (uint64_t)(nlev + 1) * (nb + 1);
     hipLaunchKernelGGL(k_sort_final, dim3((unsigned)((nfin + kScanThreads - 1) / kScanThreads)), dim3(kScanThreads), 0, s, g,

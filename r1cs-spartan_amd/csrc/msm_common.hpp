@@ -117,6 +117,9 @@ struct MsmWorkspace {
     // block of each hand-off resets its ticket)
     DBuf cnt, bintot, binbase, binsum, stage_ref, stage_fine, lvl, tickets;
     bool tickets_zeroed = false;
+    // hot buckets of the running batch (msm_sort: listed by k_sort_bins, reduced by k_accum_hot)
+    DBuf hot;
+    bool hot_on = true;  // reduce the listed hot buckets (msm_ws_set_hot; off: the weighting leaf adds them, A/B)
     // compacted-key capacity factor: raised after an overflow, so a workload whose scalars crowd some
     // rank's buckets (e.g. many equal values) stops overflowing after its first batch
     double cap_scale = 1.0;
@@ -148,13 +151,23 @@ struct MsmPlan {
 MsmPlan msm_plan(const MsmInst* ih, int ninst, const MsmShard& sh, double cap_scale);
 void msm_upload_plan(MsmWorkspace* ws, MsmPlan& p, hipStream_t s);
 
-// status words after a batch's outputs (zeroed with them by the sort's first launch): [0] status bits
+// status words after a batch's outputs (zeroed with them by the sort's first launch): [0] status bits,
+// [1] hot buckets listed (kMsmStHot; also the list's device-side counter), [2] hot buckets reduced,
+// [3] the most partials the weighting leaf added for one bucket where that exceeds 1 (else 0).
+//
+// A bucket is hot if the planned partial levels leave it more than kSeg partials: its final level
+// count v_nlev > kSeg, so v_0 > kSeg^(nlev + 1) affine-level partials, each but the first and last
+// of them a full run of seg1 references: more than (kSeg^(nlev + 1) - 1) seg1 references. At most
+// tot_refs / ((kSeg^(nlev + 1) - 1) seg1) buckets of a batch can be hot: the list's capacity.
+uint32_t msm_hot_cap(uint64_t tot_refs, uint32_t seg1, int nlev);
 // Digit / sort stage: references sorted by bucket, per-bucket offsets (offs[nb] = references), and
 // the offsets of the affine level's partials (np_off: the seg1-reference thread ranges each bucket
 // meets) and of every planned XYZZ level (lev[l]: segments of kSeg partials per bucket).
 struct MsmSorted {
     uint32_t *offs, *refs, *np_off;
     std::vector<uint32_t*> lev;
+    uint32_t* hot = nullptr;  // hot buckets (batch-local bucket indices), st[kMsmStHot] of them
+    uint32_t hot_cap = 0;
 };
 // seg1 / nlev: the affine level's references per thread and the number of XYZZ partial levels the
 // driver will run. out_dev / out_bytes: the batch's outputs and status words, zeroed by the first

@@ -308,6 +308,49 @@ __global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_accum_xyzz(const uin
     A::st(out + s, acc);
 }
 
+// ------------------------------------------------------------------ hot buckets
+// The partial levels are planned from the expected occupancy, so a bucket that skewed scalars crowd
+// (a 0 / 1 witness sends every 1 to one bucket) leaves them with hundreds of partials, which the
+// weighting leaf would add one after another on one element's lanes. k_sort_bins lists the buckets
+// left with more than kSeg partials (hot: msm_common.hpp); here one workgroup per listed bucket
+// reduces its partials in place to one, at the bucket's first slot, by a pairwise tree: round s adds
+// partial i + s into partial i for every i = 2 s k, one element's lanes (a pair in G1, a quad in G2:
+// the split addition of the weighting kernels) per pair, so the depth is log2 of the partial count
+// instead of the count. A round reads only slots that earlier rounds of the same workgroup wrote:
+// the hand-off is global memory under workgroup-scope ordering (__syncthreads: the stores are
+// complete and visible to the workgroup's waves, which share the CU's vector cache). P + P and
+// infinity partials take tree_add's own paths. The grid is fixed at plan time and the launch
+// unconditional: workgroups past the device-side count (status word kMsmStHot) exit at once.
+// One wave per SIMD: two XYZZ points live in tree_add (a G2 point is 112 registers in radix 2^29)
+// plus its temporaries need more than the 256 registers two resident waves would leave.
+static constexpr int kHotThreads = 256;
+static constexpr uint32_t kHotGrid = 64;  // workgroups at most (each takes the list entries h = block, block + grid, ..)
+template <class F>
+__global__ __launch_bounds__(kHotThreads, 1) void k_accum_hot(const uint32_t* __restrict__ hot, uint32_t cap,
+                                                              uint32_t* __restrict__ st, const uint32_t* __restrict__ off,
+                                                              Xyzz<F>* P) {
+    using A = Acc<F>;
+    using T = typename A::T;
+    constexpr uint32_t kL = TreeLanes<F>::v, ngrp = kHotThreads / kL;
+    const uint32_t nhot = min(st[kMsmStHot], cap);
+    const uint32_t grp = threadIdx.x / kL;
+    for (uint32_t h = blockIdx.x; h < nhot; h += gridDim.x) {
+        const uint32_t b = hot[h];
+        const uint32_t o = off[b], m = off[b + 1] - o;  // the bucket's partials: P[o, o + m)
+        for (uint32_t s = 1; s < m; s <<= 1) {
+            for (uint32_t i = 2 * s * grp; i + s < m; i += 2 * s * ngrp) {
+                X29<T> a, c;
+                A::ld(a, P + o + i);
+                A::ld(c, P + o + i + s);
+                tree_add<F>(a, c);
+                A::st(P + o + i, a);
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) atomicAdd(&st[kMsmStReduced], 1u);
+    }
+}
+
 // ------------------------------------------------------------------ bucket weighting: chunks + tree
 // Result = sum_j (j+1) S_j over the B = 2^(c-1) bucket sums of an instance. Node = (F, S, D) over a
 // run of consecutive buckets, with F = sum_m (m+1) X_m (local index m), S = sum X_m, D = size * S.
@@ -326,11 +369,14 @@ DEV uint32_t tree_chunk_log(uint32_t lb) { return lb - 1 < kTreeChunkLog ? lb - 
 
 // Every partial a bucket still has is added here (the partial levels are planned from the expected
 // occupancy, so a crowded bucket may arrive with several): run += X for each, then F += run.
+// hot_on: a bucket with more than kSeg partials was hot and k_accum_hot left its sum in its first
+// slot, so at most kSeg are added for any bucket. The most added for one bucket goes to status word
+// kMsmStLeafMax where it exceeds 1.
 template <class F>
 __global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_tree_chunk(
     const MsmInst* __restrict__ insts, const uint64_t* __restrict__ wp, int ninst, const uint32_t* __restrict__ node_off,
     const uint32_t* __restrict__ off, const Xyzz<F>* __restrict__ P,
-    Xyzz<F>* __restrict__ Fo, Xyzz<F>* __restrict__ So, Xyzz<F>* __restrict__ Do) {
+    Xyzz<F>* __restrict__ Fo, Xyzz<F>* __restrict__ So, Xyzz<F>* __restrict__ Do, uint32_t hot_on, uint32_t* __restrict__ st) {
     using A = Acc<F>;
     const uint64_t t = tree_elem<F>();
     if (t >= wp[ninst]) return;
@@ -347,7 +393,16 @@ __global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_tree_chunk(
     x29_set_inf(run);
     const int m = 1 << lgm;
     int j = m - 1;
-    uint32_t u = 0, nu = off[b0 + j + 1] - off[b0 + j];  // partials of bucket j added so far / to add
+    auto partials = [&](int jj) {
+        uint32_t n = off[b0 + jj + 1] - off[b0 + jj];
+        if (hot_on && n > kSeg) n = 1;
+        // (rare: the planned levels leave most buckets one partial; reported here, so no register is held for it)
+        if (n > 1 && threadIdx.x % TreeLanes<F>::v == 0 &&
+            n > __hip_atomic_load(&st[kMsmStLeafMax], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicMax(&st[kMsmStLeafMax], n);
+        return n;
+    };
+    uint32_t u = 0, nu = partials(j);  // partials of bucket j added so far / to add
 #pragma unroll 1
     for (;;) {
         const bool bucket_step = u < nu;
@@ -361,7 +416,7 @@ __global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_tree_chunk(
             if (j == 0) break;
             --j;
             u = 0;
-            nu = off[b0 + j + 1] - off[b0 + j];
+            nu = partials(j);
             continue;
         } else {
             A::ld(a, Fo + o);
@@ -375,7 +430,7 @@ __global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_tree_chunk(
             if (j == 0) break;
             --j;
             u = 0;
-            nu = off[b0 + j + 1] - off[b0 + j];
+            nu = partials(j);
         }
     }
     A::st(So + o, run);
@@ -598,6 +653,14 @@ static void msm_run_t(MsmWorkspace* ws, const MsmInst* ih, int ninst, const type
         std::swap(cur_off, nxt_off);
         cur_max_segs = nsegs;
     }
+    // hot buckets (more than kSeg partials left): each reduced to one partial in place, in `cur`
+    uint32_t* stw = (uint32_t*)((uint8_t*)out_dev + ob - 16);
+    if (ws->hot_on) {
+        kp_begin(g2 ? KP_ACCX_G2 : KP_ACCX_G1, s);
+        hipLaunchKernelGGL(k_accum_hot<F>, dim3(std::min(so.hot_cap, kHotGrid)), dim3(kHotThreads), 0, s, so.hot, so.hot_cap,
+                           stw, cur_off, cur);
+        kp_end(0.0, s);
+    }
     // bucket weighting tree over each instance's 2^lb local buckets: leaf, middle levels, top
     uint32_t tot_nodes = 0;
     for (int i = 0; i < nact; ++i) tot_nodes += pl.cnt[i];
@@ -609,7 +672,7 @@ static void msm_run_t(MsmWorkspace* ws, const MsmInst* ih, int ninst, const type
     {
         uint64_t work = pl.wp[nact];
         hipLaunchKernelGGL(k_tree_chunk<F>, dim3(tree_blocks<F>(work)), dim3(kHeavy), 0, s, pl.d_insts, pl.d_wp, nact,
-                           pl.d_noff, cur_off, cur, A3[0], A3[1], A3[2]);
+                           pl.d_noff, cur_off, cur, A3[0], A3[1], A3[2], ws->hot_on ? 1u : 0u, stw);
     }
     for (int lv = 1; lv < pl.top_from; ++lv) {
         uint64_t work = 3 * pl.wp[(size_t)lv * (nact + 1) + nact];

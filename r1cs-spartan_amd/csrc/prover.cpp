@@ -102,6 +102,13 @@ void Ctx::ensure_side() {
     SPX_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
     SPX_HIP(hipEventCreateWithFlags(&side_ev, hipEventDisableTiming));
     msm_side = msm_ws_create();
+    set_msm_hot(hot_mode);
+}
+void Ctx::set_msm_hot(int mode) {
+    hot_mode = mode;
+    const bool on = mode < 0 ? msm_hot_default() : mode == 1;
+    msm_ws_set_hot(msm, on);
+    msm_ws_set_hot(msm_side, on);
 }
 Ctx::~Ctx() {
     (void)hipSetDevice(device);
@@ -892,6 +899,19 @@ static uint32_t msm_status(const uint8_t* h, bool g2, int cnt) {
     return st;
 }
 
+// the skew words of a finished batch (not one that is about to rerun dense) into the context's totals
+static void msm_skew_fold(Ctx& C, const uint8_t* h, bool g2, int cnt) {
+    uint32_t st[4];
+    memcpy(st, h + msm_out_bytes(g2, cnt) - 16, 16);
+    ++C.skew_batches;
+    if (st[kMsmStHot]) ++C.skew_hot_batches;
+    C.skew_reduced += st[kMsmStReduced];
+    const uint64_t leaf = st[kMsmStLeafMax] ? st[kMsmStLeafMax] : 1;  // the word is written only past 1
+    uint64_t cur = C.skew_leaf_max.load();
+    while (cur < leaf && !C.skew_leaf_max.compare_exchange_weak(cur, leaf)) {
+    }
+}
+
 static MsmShard shard_of(const Comm& comm) {
     MsmShard sh;
     sh.rank = comm.rank();
@@ -934,6 +954,7 @@ static Affine<HFq> commit_finish(Ctx& C, PP& P, const Fr* z, uint64_t n, Comm& c
         commit_launch(C, P, z, n, sh);
         C.sync();
     }
+    msm_skew_fold(C, h, false, 1);
     return msm_results<HFq>(comm, h, 1)[0];
 }
 
@@ -990,6 +1011,7 @@ static Affine<HFq2> lvl0_finish(Ctx& C, PP& P, const Fr* z, int L, Comm& comm, b
         else
             C.sync();
     }
+    msm_skew_fold(C, h, true, 1);
     return msm_results<HFq2>(comm, h, 1)[0];
 }
 
@@ -1077,6 +1099,7 @@ static OpenOut open_z(Ctx& C, PP& P, const Fr* z, int L, const std::vector<HFr>&
         msm_ws_note_overflow(C.msm);  // compacted keys overflowed: once more with a slot per digit
         ++C.msm_reruns;
     }
+    if (nm) msm_skew_fold(C, h, true, nm);
     res.eval = ld_hfr(h + ob);
     std::vector<Affine<HFq2>> part = msm_results<HFq2>(comm, h, nm);
     for (int k = 0; k < nm; ++k) res.proofs[first + k] = part[k];
@@ -2493,6 +2516,7 @@ std::vector<uint8_t> k_msm(Ctx& C, bool g2, const uint8_t* bases, const uint8_t*
     C.sync();
     if (herr & 1) throw SpxError(kSerialization, "non-canonical input");
     if (herr & 2) throw SpxError(kSerialization, "base point not on the curve");
+    msm_skew_fold(C, h.data(), g2, 1);
     std::vector<uint8_t> res(ps);
     LocalComm local;
     if (g2)

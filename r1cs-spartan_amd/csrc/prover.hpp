@@ -44,6 +44,10 @@ inline bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 // Largest supported log_n / nv. Bounded by the MSM references (31-bit point index: n x 16 window
 // copies < 2^31 up to n = 2^26) and by the eq-table scratch (two halves of <= 2^13 entries each).
 static constexpr int kMaxLogN = 26;
+// The largest opening batch (levels of 2^(L-1) .. 1 scalars, L <= kMaxLogN) fits the MSM sort's bins:
+// its L - 13 levels of >= 2^14 points have 2^15 buckets each, the smaller ones together fewer than 2^12.
+static_assert((uint64_t)(kMaxLogN - 13) * (1u << 15) + (1u << 12) <= kMsmMaxBuckets,
+              "kMaxLogN: an opening batch's buckets exceed the MSM sort's bins");
 
 // owning device allocation
 struct DevMem {
@@ -209,6 +213,13 @@ struct Ctx {
     int lvl0_mode = -1;         // shared level-0 opening MSM: 1 inside the first opening's batch, 0 beside
                                 // the commitment, -1 the process default (SPX_LVL0=batch -> 1)
     std::atomic<uint64_t> msm_reruns{0};  // MSM batches rerun dense after a compacted-key overflow
+    // hot-bucket reduction of this context's MSMs: 1 on, 0 off (listed and counted only), -1 the
+    // process default (SPX_MSM_HOT=0 -> off, else on); applied to both workspaces (set_msm_hot)
+    int hot_mode = -1;
+    void set_msm_hot(int mode);
+    // folded from every finished batch's status words (msm_skew_fold): batches, batches with a hot
+    // bucket, hot buckets reduced, the most partials the weighting leaf added for one bucket
+    std::atomic<uint64_t> skew_batches{0}, skew_hot_batches{0}, skew_reduced{0}, skew_leaf_max{0};
     // one prove or round-level session at a time: both own the streams, the scratch tables, the pinned
     // carve-out and the sumcheck ticket (CtxClaim)
     std::atomic<bool> in_use{false};

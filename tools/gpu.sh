@@ -8,6 +8,8 @@
 #   bench[=ARGS]          python bench.py ARGS (default: --full, every measurement) -> TAG_bench.json
 #   samegpu=N[,ARGS]      bench.py --gpus N with every rank on GPU 0 (SPX_BENCH_SAME_GPU=1)
 #                                                                                    -> TAG_samegpuN.json
+#   skew[=ARGS]           tools/skew_bench.py ARGS (default: --headline): 0 / 1 against uniform witnesses,
+#                         hot-bucket reduction on and off                            -> TAG_skew.json, profiles/skew_bench.json
 #   profile               tools/profile_gpu.sh TAG (rocprofv3 traces + PMC passes)
 #   ab=ALT1;ALT2...       tools/ab_bench.sh TAG ALT1 ALT2 ...
 # Every step has its own time limit; the first failing step ends the script (no retries).
@@ -34,6 +36,11 @@ for step in "$@"; do
       # shellcheck disable=SC2086
       SPX_BENCH_SAME_GPU=1 timeout -k 10 700 python -u bench.py --full --gpus "$n" $extra \
         > "$O/${TAG}_samegpu${n}.json" 2> "$O/${TAG}_samegpu${n}.err" || exit $? ;;
+    skew)
+      # shellcheck disable=SC2086
+      timeout -k 10 600 python -u tools/skew_bench.py ${arg:---headline} --out "$O/${TAG}_skew_bench.json" \
+        > "$O/${TAG}_skew.json" 2> "$O/${TAG}_skew.err" || exit $?
+      cp "$O/${TAG}_skew_bench.json" profiles/skew_bench.json ;;
     profile)
       timeout -k 10 1100 bash tools/profile_gpu.sh "$TAG" || exit $? ;;
     ab)
