@@ -318,6 +318,20 @@ int spx_msm_reruns(spx_ctx *ctx, uint64_t *reruns);
  * the results are exact either way. */
 int spx_msm_skew_stats(spx_ctx *ctx, uint64_t out[4]);
 
+/* The MSM window plan. An MSM of `size` points runs `windows` signed digits of `c` bits per scalar:
+ * c = 17 with 15 windows from 2^SPX_MSM_WIDE_MIN_LOG points on (environment, default 18; 0: never;
+ * otherwise at least 8; read when a public parameter is loaded or generated and at spx_msm_g1 / _g2),
+ * c = 16 with 16 windows for the other MSMs of >= 2^14 points, narrower windows below.
+ * spx_msm_window_plan: the plan spx_msm_g1 / _g2 would take now (no GPU needed).
+ * spx_pp_window_plan: the plan fixed in a public parameter, level = -1 for the commitment bases,
+ * 0 .. nv - 1 for the opening levels (2^(nv - level - 1) points); a level at or above the threshold
+ * keeps c = 16 where 2^16 buckets more would pass an opening batch's bucket limit (2^19). */
+int spx_msm_window_plan(uint64_t size, int *c, int *windows);
+/* c[0 .. nv - 1]: the window bits a public parameter of nv variables (1 .. 26) would fix for its
+ * opening levels now (no GPU needed) */
+int spx_msm_level_plan(int nv, int *c);
+int spx_pp_window_plan(spx_pp *pp, int level, int *c, int *windows);
+
 /* ---- kernel-level entry points (parity tests) ---- */
 int spx_sum_over_y(spx_ctx *ctx, const spx_csr *m, const uint8_t *z, uint8_t *out);
 int spx_eval_on_x(spx_ctx *ctx, const spx_csr *m, const uint8_t *r_x, uint8_t *out);

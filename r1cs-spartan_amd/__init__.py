@@ -96,6 +96,9 @@ EXPORTED = [
     "spx_ctx_comm_allgather",
     "spx_msm_reruns",
     "spx_msm_skew_stats",
+    "spx_msm_window_plan",
+    "spx_msm_level_plan",
+    "spx_pp_window_plan",
     "spx_ctx_mem_info",
     "spx_ctx_set_sync_poll",
     "spx_ctx_set_group",
@@ -187,6 +190,11 @@ def lib():
     if hasattr(L, "spx_ctx_set_msm_hot") or not os.environ.get("SPX_LIB_PATH"):
         L.spx_ctx_set_msm_hot.argtypes = [vp, ctypes.c_int]
         L.spx_msm_skew_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "spx_msm_window_plan") or not os.environ.get("SPX_LIB_PATH"):
+        pint = ctypes.POINTER(ctypes.c_int)
+        L.spx_msm_window_plan.argtypes = [ctypes.c_uint64, pint, pint]
+        L.spx_msm_level_plan.argtypes = [ctypes.c_int, pint]
+        L.spx_pp_window_plan.argtypes = [vp, ctypes.c_int, pint, pint]
     if hasattr(L, "spx_comm_hub_create_rccl") or not os.environ.get("SPX_LIB_PATH"):  # A/B builds may predate the hub
         L.spx_comm_hub_create_rccl.argtypes = [u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
         L.spx_comm_hub_create_shm.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
@@ -570,6 +578,13 @@ class PublicParameter:
         _check(lib().spx_pp_load(ctx.h, bytes(data), len(data), ctypes.byref(h)))
         return PublicParameter(ctx, h, int.from_bytes(data[:8], "little"))
 
+    def window_plan(self, level):
+        """(window bits, windows) of the commitment MSM (level -1) or of opening level 0 .. nv - 1
+        (spx_pp_window_plan)"""
+        c, w = ctypes.c_int(0), ctypes.c_int(0)
+        _check(lib().spx_pp_window_plan(self.h, int(level), ctypes.byref(c), ctypes.byref(w)))
+        return c.value, w.value
+
     def serialize_uncompressed(self):
         n = ctypes.c_size_t(0)
         _check(lib().spx_pp_serialize(self.h, None, 0, ctypes.byref(n)))
@@ -928,6 +943,20 @@ class MLPolyCommit:
         pf = ctypes.create_string_buffer(96 + 8 + 96 * nv)
         _check(lib().spx_open(pp.ctx.h, pp.h, tb, nv, pb, ev, pf))
         return ev.raw, pf.raw
+
+
+def msm_window_plan(size):
+    """(window bits, windows) an MSM of `size` points takes now (spx_msm_window_plan; no GPU needed)"""
+    c, w = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().spx_msm_window_plan(int(size), ctypes.byref(c), ctypes.byref(w)))
+    return c.value, w.value
+
+
+def msm_level_plan(nv):
+    """window bits of the nv opening levels of an nv-variable public parameter (spx_msm_level_plan)"""
+    c = (ctypes.c_int * int(nv))()
+    _check(lib().spx_msm_level_plan(int(nv), c))
+    return [int(x) for x in c]
 
 
 def msm_g1(ctx, bases_uncompressed, scalars):

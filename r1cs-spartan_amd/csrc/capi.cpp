@@ -307,6 +307,30 @@ int spx_pp_serialize(spx_pp* pp, uint8_t* out, size_t cap, size_t* len) {
         copy_out(spx::pp_serialize(*pp->ctx->c, *pp->p), out, cap, len);
     });
 }
+int spx_pp_window_plan(spx_pp* pp, int level, int* c, int* windows) {
+    return guard([&] {
+        if (!pp || !c || !windows) spx::invalid("null argument");
+        const spx::PP& P = *pp->p;
+        if (level < -1 || level >= P.nv) spx::invalid("level out of range");
+        *c = level < 0 ? P.g1_c : P.g2_c[level];
+        *windows = level < 0 ? P.g1_W : P.g2_W[level];
+    });
+}
+int spx_msm_window_plan(uint64_t size, int* c, int* windows) {
+    return guard([&] {
+        if (!c || !windows) spx::invalid("null argument");
+        *c = spx::window_bits_for(size, spx::msm_wide_min_log());
+        *windows = spx::windows_for(*c);
+    });
+}
+int spx_msm_level_plan(int nv, int* c) {
+    return guard([&] {
+        if (!c) spx::invalid("null argument");
+        if (nv < 1 || nv > spx::kMaxLogN) spx::invalid("nv out of range");
+        const std::vector<int> plan = spx::g2_window_plan(nv, spx::msm_wide_min_log());
+        std::copy(plan.begin(), plan.end(), c);
+    });
+}
 int spx_pp_free(spx_pp* pp) {
     return guard([&] {
         if (pp) set_dev(pp->ctx);

@@ -287,6 +287,11 @@ enum { kMsmStHot = 1, kMsmStReduced = 2, kMsmStLeafMax = 3 };
 // buckets one batch may hold: the sort's 2048 bins of <= 2^8 buckets (msm_common.hip); prover.hpp ties
 // kMaxLogN to it
 static constexpr uint64_t kMsmMaxBuckets = 2048ull << 8;
+// The wide window plan: c = 17 takes 15 windows (17 x 15 = 255 bits of an Fr scalar), which holds
+// only because the digit pass replaces a scalar above (r - 1) / 2 by its negative and flips the sign
+// of its references (msm_common.hip, Digits::fold_half). Every other c takes ceil(256 / c) windows.
+static constexpr uint32_t kMsmWideBits = 17, kMsmWideWindows = 15;
+static constexpr uint32_t msm_windows(uint32_t c) { return c == kMsmWideBits ? kMsmWideWindows : (256 + c - 1) / c; }
 struct MsmWorkspace;  // opaque, owned by the host side (msm.hip)
 MsmWorkspace* msm_ws_create();
 void msm_ws_destroy(MsmWorkspace* ws);

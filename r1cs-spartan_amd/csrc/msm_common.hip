@@ -49,12 +49,35 @@ struct Digits {
         carry = v > half;
         return carry ? (int32_t)v - (int32_t)full : (int32_t)v;
     }
-    // c = 16 (every MSM of >= 2^14 points): window w is half-word w of the scalar, so nothing is
-    // shifted (w a constant in the unrolled loops); the same signed digits as next(16) in order
+    // c = 16 (MSMs of >= 2^14 points below the wide threshold): window w is half-word w of the scalar,
+    // so nothing is shifted (w a constant in the unrolled loops); the same signed digits as next(16) in order
     DEV int32_t at16(uint32_t w) {
         const uint32_t v = ((s[w >> 1] >> (16 * (w & 1))) & 0xFFFFu) + carry;
         carry = v > 0x8000u;
         return carry ? (int32_t)v - 0x10000 : (int32_t)v;
+    }
+    // c = 17 (kMsmWideBits): s > (r - 1) / 2 is replaced by r - s and the caller flips the sign of every
+    // reference of the scalar (returns that flip, 0 or bit 31). The value left is < 2^254, so its top
+    // digit (bits 238..253 plus a carry) is <= 0xE7DB + 1 and no carry leaves window 14: 15 windows do.
+    DEV uint32_t fold_half() {
+        uint32_t t[8];
+        unsigned br = 0, lt = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[k] = __builtin_subc(kFrP[k], s[k], br, &br);  // r - s (s < r)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) (void)__builtin_subc(t[k], s[k], lt, &lt);  // r - s < s <=> s > (r - 1) / 2
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s[k] = lt ? t[k] : s[k];
+        return lt ? 0x80000000u : 0u;
+    }
+    // window w of 17 bits at bit 17 w (w a constant in the unrolled loop: static word and shift); the
+    // same signed digits as next(17) in order
+    DEV int32_t at17(uint32_t w) {
+        const uint32_t bit = 17 * w, k = bit >> 5, sh = bit & 31;
+        const uint64_t two = (uint64_t)s[k] | (k < 7 ? (uint64_t)s[k < 7 ? k + 1 : 7] << 32 : 0ull);
+        const uint32_t v = ((uint32_t)(two >> sh) & 0x1FFFFu) + carry;
+        carry = v > 0x10000u;
+        return carry ? (int32_t)v - 0x20000 : (int32_t)v;
     }
 };
 // the digit's bucket if it is one of this rank's (local index in the batch), else ~0u
@@ -67,9 +90,10 @@ DEV uint32_t digit_key(const MsmInst& I, int32_t d) {
 DEV uint32_t digit_ref(const MsmInst& I, uint32_t w, uint64_t j, int32_t d) {
     return (uint32_t)(I.pts_off + (uint64_t)w * I.stride + j) | (d < 0 ? 0x80000000u : 0u);
 }
-// The digits of batch scalar g that land in one of this rank's buckets. c = 16 with 16 windows (every
-// MSM of >= 2^14 points): all 16 keys and references into registers (unrolled: static indices), so a
-// caller can issue their 16 LDS atomics back to back; otherwise f(key, ref) per digit.
+// The digits of batch scalar g that land in one of this rank's buckets. c = 16 with 16 windows (MSMs
+// of >= 2^14 points) and c = 17 with 15 windows (the wide MSMs; slot 15 empty): all keys and references
+// into registers (unrolled: static indices), so a caller can issue their LDS atomics back to back;
+// otherwise f(key, ref) per digit.
 struct Keys16 {
     uint32_t key[16], ref[16];  // key ~0u: not this rank's / zero digit
 };
@@ -94,10 +118,24 @@ DEV bool scalar_keys(const MsmInst* __restrict__ insts, const uint64_t* __restri
         }
         return true;
     }
+    // a wide instance (c = 17, 15 windows): the one place that decides the negation, for all three
+    // sort kernels that derive the digits
+    const uint32_t flip = I.c == kMsmWideBits ? d.fold_half() : 0u;
+    if (I.c == kMsmWideBits && I.W == kMsmWideWindows) {
+#pragma unroll
+        for (uint32_t w = 0; w < kMsmWideWindows; ++w) {
+            const int32_t dg = d.at17(w);
+            k16.key[w] = digit_key(I, dg);
+            k16.ref[w] = digit_ref(I, w, j, dg) ^ flip;
+        }
+        k16.key[15] = ~0u;  // the 16th slot stays empty
+        k16.ref[15] = 0u;
+        return true;
+    }
     for (uint32_t w = 0; w < I.W; ++w) {
         const int32_t dg = d.next(I.c);
         const uint32_t key = digit_key(I, dg);
-        if (key != ~0u) f(key, digit_ref(I, w, j, dg));
+        if (key != ~0u) f(key, digit_ref(I, w, j, dg) ^ flip);
     }
     return false;
 }
@@ -269,7 +307,7 @@ __global__ __launch_bounds__(NT) void k_sort_scan(uint32_t* __restrict__ cnt, So
     }
 }
 
-// K3. Per iteration (kTileThreads scalars, one per thread): every c = 16 scalar's <= 16 pairs take an
+// K3. Per iteration (kTileThreads scalars, one per thread): every c = 16 or 17 scalar's <= 16 pairs take an
 // LDS rank in their bin (lcnt), the counts are scanned over the bins (lst = this iteration's run
 // start of each bin), the pairs are placed in bin order in LDS (sk, sr), and thread i writes pair i
 // to pos[bin] + (i - lst[bin]): consecutive threads, consecutive addresses inside a bin's run. A
@@ -427,7 +465,9 @@ __global__ __launch_bounds__(NT) void k_sort_bins(SortGeom g, const uint32_t* __
     const uint32_t base = binbase[bin], n = over ? 0u : binbase[bin + 1] - base;
     // the bin's pairs read as aligned quads: element e of quad q is pair a0 + 4 q + e, valid in
     // [head, head + n) (the staging buffers have 16 bytes of slack past their capacity)
-    const uint32_t a0 = base & ~3u, head = base - a0, nq = (head + n + 3) / 4;
+    // (no quad of an empty bin is read: after an overflow the bases count every pair of the batch and
+    // lie past the staging buffers, which hold the planned capacity only)
+    const uint32_t a0 = base & ~3u, head = base - a0, nq = n ? (head + n + 3) / 4 : 0u;
     if (f < 256) L.h[f] = 0;
     __syncthreads();
     for (uint32_t q = f; q < nq; q += NT) {
@@ -576,6 +616,7 @@ MsmPlan msm_plan(const MsmInst* ih, int ninst, const MsmShard& sh, double cap_sc
         MsmInst I = ih[i];
         if (!I.size) continue;  // empty MSM: infinity
         if (I.c < 3 || I.c > 24) throw std::runtime_error("MSM window bits out of range");
+        if (I.W < msm_windows(I.c)) throw std::runtime_error("MSM: too few windows for the window bits");
         const uint32_t lbf = I.c - 1;  // log2 of the instance's buckets
         if (G > 1 && (int)lbf - g >= 2) {  // split: buckets dealt round-robin over the ranks
             I.lb = lbf - g;

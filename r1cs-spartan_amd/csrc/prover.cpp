@@ -128,13 +128,47 @@ uint8_t* Ctx::pin_at(size_t off, size_t bytes, size_t region) {
 
 
 // ====================================================================== public parameters
-// Pippenger window bits: 16 for >= 2^14 points (wider windows for >= 2^18 and narrower ones for
-// 2^14-2^17 measured slower or equal: profiles/r02_ab6_window_bits.jsonl, r02_ab7_window_mid.jsonl)
-int window_bits_for(uint64_t size) {
+// Pippenger window bits: 16 for >= 2^14 points (c = 18..20 for >= 2^18 and narrower ones for
+// 2^14-2^17 measured slower or equal: profiles/r02_ab6_window_bits.jsonl, r02_ab7_window_mid.jsonl).
+// From 2^wide_min_log points on: 17 bits, which take 15 windows where 16 bits take 16 (a sixteenth
+// fewer mixed additions for twice the buckets; kernels.hpp, kMsmWideBits). wide_min_log 0: never.
+// Thresholds 2^16 .. 2^19 and off against the 16-bit build at 2^20, alternating on one box: 2^18 is
+// the best, +2.3% (profiles/r07/r07b_ab_wide_thresholds.jsonl).
+int window_bits_for(uint64_t size, int wide_min_log) {
     const int k = size ? ilog2(size) : 0;
+    if (wide_min_log > 0 && k >= wide_min_log) return (int)kMsmWideBits;
     return k >= 14 ? 16 : std::max(3, k - 2);
 }
-static int windows_for(int c) { return (256 + c - 1) / c; }
+int windows_for(int c) { return (int)msm_windows((uint32_t)c); }
+// SPX_MSM_WIDE_MIN_LOG: log2 of the smallest MSM that takes the wide plan (0: none; otherwise at
+// least 8). Read when a public parameter is preprocessed and at the stand-alone MSM entry.
+int msm_wide_min_log() {
+    const char* e = getenv("SPX_MSM_WIDE_MIN_LOG");
+    if (!e || !*e) return kMsmWideMinLogDefault;
+    const int v = atoi(e);
+    return v <= 0 ? 0 : std::max(v, 8);
+}
+// Window bits of the G2 levels of an nv-variable public parameter (level i: 2^(nv - i - 1) points).
+// All levels of an opening may run as one batch (level 0 included in the level-0 batch mode), and a
+// batch holds at most kMsmMaxBuckets buckets: the wide plan goes to the largest levels first and the
+// remaining candidates keep 16 bits once another 2^16 buckets would pass the limit.
+std::vector<int> g2_window_plan(int nv, int wide_min_log) {
+    std::vector<int> c(nv);
+    uint64_t buckets = 0;
+    for (int i = 0; i < nv; ++i) {
+        c[i] = window_bits_for(1ull << (nv - i - 1), 0);
+        buckets += 1ull << (c[i] - 1);
+    }
+    for (int i = 0; i < nv; ++i) {
+        const int cw = window_bits_for(1ull << (nv - i - 1), wide_min_log);
+        if (cw == c[i]) break;  // smaller levels are below the threshold too
+        const uint64_t with = buckets - (1ull << (c[i] - 1)) + (1ull << (cw - 1));
+        if (with > kMsmMaxBuckets) break;
+        c[i] = cw;
+        buckets = with;
+    }
+    return c;
+}
 
 // dst: G2Aff rows, or G1Slot rows (128-byte slots) for G1
 template <class A, class D>
@@ -165,17 +199,17 @@ static void precompute_level(Ctx& C, const A* raw, uint64_t count, bool pair, in
 void pp_preprocess(Ctx& C, PP& P) {
     const int nv = P.nv;
     const uint64_t n = 1ull << nv;
-    P.g1_c = window_bits_for(n);
+    const int wide = msm_wide_min_log();
+    P.g1_c = window_bits_for(n, wide);
     P.g1_W = windows_for(P.g1_c);
     P.g1_pre.alloc(sizeof(G1Slot) * n * P.g1_W);
     precompute_level(C, P.g1_level(0), n, false, P.g1_c, P.g1_W, P.g1_pre.as<G1Slot>());
     P.g2_off.assign(nv + 1, 0);
-    P.g2_c.assign(nv, 0);
+    P.g2_c = g2_window_plan(nv, wide);
     P.g2_W.assign(nv, 0);
     uint64_t tot = 0;
     for (int i = 0; i < nv; ++i) {
         uint64_t cnt = 1ull << (nv - i - 1);
-        P.g2_c[i] = window_bits_for(cnt);
         P.g2_W[i] = windows_for(P.g2_c[i]);
         P.g2_off[i] = tot;
         tot += cnt * P.g2_W[i];
@@ -2496,7 +2530,7 @@ std::vector<uint8_t> k_msm(Ctx& C, bool g2, const uint8_t* bases, const uint8_t*
     else
         launch_points_from_bytes_g1(raw.as<G1Aff>(), n, err.as<int>(), C.stream);
     MsmInst I{};
-    I.c = (uint32_t)window_bits_for(n);
+    I.c = (uint32_t)window_bits_for(n, msm_wide_min_log());
     I.W = (uint32_t)windows_for((int)I.c);
     I.size = (uint32_t)n;
     I.stride = (uint32_t)n;

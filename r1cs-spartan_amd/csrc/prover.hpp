@@ -41,13 +41,20 @@ inline void invalid(const std::string& m) { throw SpxError(kInvalidArgument, m);
 inline int ilog2(uint64_t x) { return 63 - __builtin_clzll(x); }
 inline bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 
-// Largest supported log_n / nv. Bounded by the MSM references (31-bit point index: n x 16 window
+// Largest supported log_n / nv. Bounded by the MSM references (31-bit point index: n x 15 or 16 window
 // copies < 2^31 up to n = 2^26) and by the eq-table scratch (two halves of <= 2^13 entries each).
 static constexpr int kMaxLogN = 26;
 // The largest opening batch (levels of 2^(L-1) .. 1 scalars, L <= kMaxLogN) fits the MSM sort's bins:
 // its L - 13 levels of >= 2^14 points have 2^15 buckets each, the smaller ones together fewer than 2^12.
+// That is the plan with every level at 16 bits; g2_window_plan widens levels to 17 bits (2^16 buckets),
+// the largest first, only while the batch still fits, so the bound holds for every threshold. At
+// kMaxLogN itself the largest level can still go wide.
 static_assert((uint64_t)(kMaxLogN - 13) * (1u << 15) + (1u << 12) <= kMsmMaxBuckets,
               "kMaxLogN: an opening batch's buckets exceed the MSM sort's bins");
+static_assert((uint64_t)(kMaxLogN - 14) * (1u << 15) + (1u << (kMsmWideBits - 1)) + (1u << 12) <= kMsmMaxBuckets,
+              "kMaxLogN: no room for one wide level in an opening batch");
+// Default of SPX_MSM_WIDE_MIN_LOG: MSMs of >= 2^18 points take the wide plan
+static constexpr int kMsmWideMinLogDefault = 18;
 
 // owning device allocation
 struct DevMem {
@@ -292,7 +299,11 @@ struct PP {
     G2Aff* g2_level(int i) const { return g2_raw_mem.as<G2Aff>() + lvl_off[i]; }
 };
 void pp_preprocess(Ctx& C, PP& P);
-int window_bits_for(uint64_t size);
+// The MSM window plan (prover.cpp): bits and windows by size, SPX_MSM_WIDE_MIN_LOG, the G2 levels' bits
+int window_bits_for(uint64_t size, int wide_min_log);
+int windows_for(int c);
+int msm_wide_min_log();
+std::vector<int> g2_window_plan(int nv, int wide_min_log);
 
 // ---------------------------------------------------------------- index
 struct HostCsr {
