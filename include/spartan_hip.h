@@ -235,12 +235,39 @@ int spx_host_phase_stats(uint64_t out[21]);
  * The matrix evaluation runs on the ctx's GPU; the index must be built on a single-rank context. */
 int spx_verify(spx_ctx *ctx, spx_pk *idx, const uint8_t *v, size_t nv, const uint8_t *proof, size_t len,
                const uint8_t *vp, size_t vp_len, const spx_prove_opts *opts);
+/* spx_verify for nproofs proofs of one index under one verifier parameter (lib.rs:147-212 per proof; the
+ * mKZG checks, verify.rs:12-45, of the whole batch folded into one product of log_n + 2 pairings by a
+ * random linear combination). v[j] / nv[j] / proofs[j] / lens[j]: proof j's public input
+ * and bytes. entropy32: 32 bytes mixed into the coefficients, or NULL. status[j] receives what spx_verify
+ * returns for proof j alone. Returns SPX_OK if every proof is accepted, otherwise the status of the
+ * lowest-index rejected proof with that proof's message in spx_last_error. An error of the call itself
+ * (a NULL, nproofs < 1, an index of a sharded context, a bad vp, a context in use) returns before
+ * status[] is touched. The proofs' points are decompressed and combined on the ctx's GPU. */
+int spx_verify_many(spx_ctx *ctx, spx_pk *idx, const uint8_t *const *v, const size_t *nv,
+                    const uint8_t *const *proofs, const size_t *lens, int nproofs,
+                    const uint8_t *vp, size_t vp_len, const spx_prove_opts *opts,
+                    const uint8_t *entropy32 /* may be NULL */, int *status /* nproofs */);
+/* the coefficients spx_verify_many takes for these arguments: out = 2 nproofs canonical Fr (32 B each),
+ * rho_{j,o} at 2 j + o for proof j's opening o (0: at r_v, 1: at r_y). With seed = BLAKE2s-256 (RFC 7693,
+ * unkeyed) of "spx-verify-many-v1" || vp || entropy32 (zeros if NULL) || for each proof LE64(nv_j) || v_j ||
+ * LE64(len_j) || proof_j, rho_{j,o} = the low 128 bits (little-endian) of BLAKE2s-256(seed || LE64(2 j + o)),
+ * or 1 if those are zero. Host only, no GPU. */
+int spx_verify_many_coeffs(const uint8_t *const *v, const size_t *nv, const uint8_t *const *proofs,
+                           const size_t *lens, int nproofs, const uint8_t *vp, size_t vp_len,
+                           const uint8_t *entropy32 /* may be NULL */, uint8_t *out);
+/* spx_verify_many on this context, cumulative: out[0] batches run (one combined pairing check each),
+ * out[1] pairs given to the Miller loop by the batched path (log_n + 2 per batch), out[2] proofs sent to
+ * the single-proof path, out[3] points decompressed on the GPU */
+int spx_verify_stats(spx_ctx *ctx, uint64_t out[4]);
 /* VerifierParameter of a keygen-generated PP (spx_pp_generate; setup.rs:91-101), uncompressed bytes */
 int spx_vp_from_pp(spx_pp *pp, uint8_t *out, size_t cap, size_t *len);
 /* prod_i e(P_i, Q_i) == 1 over n pairs (uncompressed G1 96 B / G2 192 B each); host only, no GPU
  * (E::product_of_pairings as used by verify.rs:12-45) */
 int spx_pairing_check(const uint8_t *g1, const uint8_t *g2, size_t n, int *is_one);
-/* per-phase device timings of the last prove on this ctx, microseconds */
+/* per-phase device timings of the last prove on this ctx, microseconds. After
+ * spx_verify_many: host wall microseconds of its seven phases, in order (0 for one that did not run):
+ * parse and transcript replay; points to the GPU with the algebraic checks; the wait for their
+ * decompression; matrix evaluations; combinations; the pairing product; single-proof path */
 int spx_last_timings(spx_ctx *ctx, double *out, int cap, int *n);
 
 /* ---- R1CS front-end: ark-relations ConstraintSystem semantics ----
@@ -343,6 +370,18 @@ int spx_sumcheck_round(spx_ctx *ctx, const uint8_t *f, const uint8_t *g, size_t 
                        uint8_t *evals_out, uint8_t *f_out, uint8_t *g_out);
 int spx_msm_g1(spx_ctx *ctx, const uint8_t *bases, const uint8_t *scalars, size_t n, uint8_t *out96);
 int spx_msm_g2(spx_ctx *ctx, const uint8_t *bases, const uint8_t *scalars, size_t n, uint8_t *out192);
+/* the batch verifier's kernels. Decompression of n ark-serialize compressed points (48 / 96 B each) to
+ * uncompressed ones (96 / 192 B): ok[j] = 1 for an accepted point (infinity carries the ark flag), 0 for
+ * a non-canonical x or an x with no point on the curve (its output bytes are zero). */
+int spx_g1_decompress(spx_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out_uncompressed, uint8_t *ok);
+int spx_g2_decompress(spx_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out_uncompressed, uint8_t *ok);
+/* out[s] = sum_{seg_off[s] <= i < seg_off[s + 1]} scalar_i base_i for n uncompressed bases and n canonical
+ * Fr scalars; seg_off: nseg + 1 ascending offsets from 0 to n. Infinity carries the ark flag in both
+ * directions. */
+int spx_lincomb_g1(spx_ctx *ctx, const uint8_t *bases_uncompressed, const uint8_t *scalars, size_t n,
+                   const uint64_t *seg_off, size_t nseg, uint8_t *out_uncompressed);
+int spx_lincomb_g2(spx_ctx *ctx, const uint8_t *bases_uncompressed, const uint8_t *scalars, size_t n,
+                   const uint64_t *seg_off, size_t nseg, uint8_t *out_uncompressed);
 int spx_commit(spx_ctx *ctx, spx_pp *pp, const uint8_t *table, int nv, uint8_t *out56);
 /* proof_out: Proof{h, proofs} compressed = 96 + 8 + 96 * nv bytes */
 int spx_open(spx_ctx *ctx, spx_pp *pp, const uint8_t *table, int nv, const uint8_t *point, uint8_t *eval_out,

@@ -127,6 +127,9 @@ EXPORTED = [
     "spx_cs_is_satisfied",
     "spx_cs_matrices",
     "spx_verify",
+    "spx_verify_many",
+    "spx_verify_many_coeffs",
+    "spx_verify_stats",
     "spx_vp_from_pp",
     "spx_pairing_check",
     "spx_prover_init",
@@ -144,6 +147,10 @@ EXPORTED = [
     "spx_eval_on_x",
     "spx_msm_g1",
     "spx_msm_g2",
+    "spx_g1_decompress",
+    "spx_g2_decompress",
+    "spx_lincomb_g1",
+    "spx_lincomb_g2",
     "spx_commit",
     "spx_open",
 ]
@@ -221,6 +228,16 @@ def lib():
     L.spx_prove_many.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, ctypes.POINTER(vp), ctypes.c_int, vp,
                                  ctypes.POINTER(_Opts), ctypes.c_void_p, sz, ctypes.POINTER(sz)]
     L.spx_verify.argtypes = [vp, vp, u8p, sz, u8p, sz, u8p, sz, ctypes.POINTER(_Opts)]
+    if hasattr(L, "spx_verify_many") or not os.environ.get("SPX_LIB_PATH"):  # A/B builds may predate it
+        pp8, psz_ = ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz)
+        L.spx_verify_many.argtypes = [vp, vp, pp8, psz_, pp8, psz_, ctypes.c_int, u8p, sz, ctypes.POINTER(_Opts), u8p,
+                                      ctypes.POINTER(ctypes.c_int)]
+        L.spx_verify_many_coeffs.argtypes = [pp8, psz_, pp8, psz_, ctypes.c_int, u8p, sz, u8p, ctypes.c_void_p]
+        L.spx_verify_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.spx_g1_decompress.argtypes = [vp, u8p, sz, ctypes.c_void_p, ctypes.c_void_p]
+        L.spx_g2_decompress.argtypes = [vp, u8p, sz, ctypes.c_void_p, ctypes.c_void_p]
+        L.spx_lincomb_g1.argtypes = [vp, u8p, u8p, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_void_p]
+        L.spx_lincomb_g2.argtypes = [vp, u8p, u8p, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_void_p]
     if hasattr(L, "spx_hash_stats") or not os.environ.get("SPX_LIB_PATH"):
         L.spx_hash_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.spx_vp_from_pp.argtypes = [vp, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
@@ -717,6 +734,28 @@ class MLArgumentForR1CS:
                                 ctypes.byref(o)))
         return True
 
+    @staticmethod
+    def verify_many(pk, vs, proofs, vp, mode="fs", seed=0, cached=False, entropy=None):
+        """spx_verify_many: the proofs of one index under one verifier parameter, their mKZG checks folded
+        into one product of pairings. Returns a list with True or the exception instance verify() would
+        raise, per proof. An error of the call itself raises."""
+        va, na, pa, la, k = _many_args(vs, proofs)
+        o = _opts(mode, seed, cached)
+        st = (ctypes.c_int * k)(*([-1] * k))
+        rc = lib().spx_verify_many(pk.ctx.h, pk.h, va, na, pa, la, k, bytes(vp), len(vp), ctypes.byref(o),
+                                   _entropy(entropy), st)
+        if rc != 0 and all(x == -1 for x in st):
+            _check(rc)  # the call itself failed: status[] untouched
+        out, first = [], lib().spx_last_error().decode(errors="replace")
+        for j in range(k):
+            if st[j] == 0:
+                out.append(True)
+                continue
+            # spx_last_error holds the lowest-index rejected proof's message; the others carry their kind
+            out.append(_ERRORS.get(st[j], SpartanError)(first if first is not None else "proof %d rejected" % j))
+            first = None
+        return out
+
 
 class InteractiveProver:
     """The reference's round-level prover (src/ahp/prover.rs:109-281) over spx_prover_*: construct
@@ -896,6 +935,87 @@ def verifier_parameter(pp):
     n = ctypes.c_size_t(0)
     _check(lib().spx_vp_from_pp(pp.h, out, cap, ctypes.byref(n)))
     return out.raw[: n.value]
+
+
+def _many_args(vs, proofs):
+    k = len(proofs)
+    if k != len(vs):
+        raise InvalidArgument("one public input per proof")
+    vb = [_as_bytes(v) for v in vs]
+    pb = [bytes(p) for p in proofs]
+    va = (ctypes.c_char_p * max(k, 1))(*vb)
+    pa = (ctypes.c_char_p * max(k, 1))(*pb)
+    na = (ctypes.c_size_t * max(k, 1))(*[len(b) // 32 for b in vb])
+    la = (ctypes.c_size_t * max(k, 1))(*[len(b) for b in pb])
+    return va, na, pa, la, k
+
+
+def _entropy(entropy):
+    if entropy is None:
+        return None
+    e = bytes(entropy)
+    if len(e) != 32:
+        raise InvalidArgument("entropy must be 32 bytes")
+    return e
+
+
+def verify_many_coeffs(vs, proofs, vp, entropy=None):
+    """The 2 len(proofs) coefficients of verify_many (spx_verify_many_coeffs; no GPU), as ints."""
+    va, na, pa, la, k = _many_args(vs, proofs)
+    out = ctypes.create_string_buffer(64 * max(k, 1))
+    _check(lib().spx_verify_many_coeffs(va, na, pa, la, k, bytes(vp), len(vp), _entropy(entropy), out))
+    return fr_ints(out.raw[: 64 * k])
+
+
+def verify_stats(ctx):
+    """(batches run, pairs given to the Miller loop by the batched path, proofs sent to the single-proof
+    path, points decompressed on the GPU) of verify_many on this context, cumulative"""
+    out = (ctypes.c_uint64 * 4)()
+    _check(lib().spx_verify_stats(ctx.h, out))
+    return tuple(int(x) for x in out)
+
+
+def _decompress(fn, ctx, data, cs):
+    data = bytes(data)
+    if not data or len(data) % cs:
+        raise InvalidArgument("compressed points are %d bytes each" % cs)
+    n = len(data) // cs
+    out = ctypes.create_string_buffer(2 * cs * n)
+    ok = ctypes.create_string_buffer(n)
+    _check(fn(ctx.h, data, n, out, ok))
+    return out.raw, [b != 0 for b in ok.raw]
+
+
+def g1_decompress(ctx, compressed):
+    """(uncompressed bytes, ok flags) of concatenated 48-byte compressed G1 points (spx_g1_decompress)"""
+    return _decompress(lib().spx_g1_decompress, ctx, compressed, 48)
+
+
+def g2_decompress(ctx, compressed):
+    return _decompress(lib().spx_g2_decompress, ctx, compressed, 96)
+
+
+def _lincomb(fn, ctx, bases, scalars, seg_off, ps):
+    bb, sb = bytes(bases), _as_bytes(scalars)
+    n = len(sb) // 32
+    if n == 0 or len(bb) != ps * n:
+        raise InvalidArgument("one %d-byte base per scalar" % ps)
+    seg = [int(x) for x in seg_off]
+    if len(seg) < 2:
+        raise InvalidArgument("segment offsets: nseg + 1 entries")
+    so = (ctypes.c_uint64 * len(seg))(*seg)
+    out = ctypes.create_string_buffer(ps * (len(seg) - 1))
+    _check(fn(ctx.h, bb, sb, n, so, len(seg) - 1, out))
+    return [out.raw[ps * i : ps * (i + 1)] for i in range(len(seg) - 1)]
+
+
+def lincomb_g1(ctx, bases_uncompressed, scalars, seg_off):
+    """[sum over segment s of scalar_i base_i] as uncompressed points (spx_lincomb_g1)"""
+    return _lincomb(lib().spx_lincomb_g1, ctx, bases_uncompressed, scalars, seg_off, 96)
+
+
+def lincomb_g2(ctx, bases_uncompressed, scalars, seg_off):
+    return _lincomb(lib().spx_lincomb_g2, ctx, bases_uncompressed, scalars, seg_off, 192)
 
 
 def pairing_product_is_one(g1_uncompressed, g2_uncompressed):

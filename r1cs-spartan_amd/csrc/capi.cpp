@@ -632,6 +632,47 @@ int spx_verify(spx_ctx* ctx, spx_pk* idx, const uint8_t* v, size_t nv, const uin
         spx::verify(*ctx->c, *idx->i, v, nv, proof, len, spx::vp_load(vp, vp_len), opts_of(opts));
     });
 }
+int spx_verify_many(spx_ctx* ctx, spx_pk* idx, const uint8_t* const* v, const size_t* nv, const uint8_t* const* proofs,
+                    const size_t* lens, int nproofs, const uint8_t* vp, size_t vp_len, const spx_prove_opts* opts,
+                    const uint8_t* entropy32, int* status) {
+    std::vector<int> st;
+    std::vector<std::string> msgs;
+    const int rc = guard([&] {
+        if (!idx || !v || !nv || !proofs || !lens || !vp || !status) spx::invalid("null argument");
+        if (nproofs < 1) spx::invalid("nproofs must be at least 1");
+        for (int j = 0; j < nproofs; ++j)
+            if ((nv[j] && !v[j]) || (lens[j] && !proofs[j])) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::verify_many(*ctx->c, *idx->i, v, nv, proofs, lens, nproofs, spx::vp_load(vp, vp_len), vp, vp_len,
+                         opts_of(opts), entropy32, st, msgs);
+    });
+    if (rc != SPX_OK) return rc;  // an error of the call itself: status[] untouched
+    for (int j = 0; j < nproofs; ++j) status[j] = st[j];
+    for (int j = 0; j < nproofs; ++j)
+        if (st[j] != SPX_OK) {
+            g_err = msgs[j];
+            return st[j];
+        }
+    return SPX_OK;
+}
+int spx_verify_many_coeffs(const uint8_t* const* v, const size_t* nv, const uint8_t* const* proofs, const size_t* lens,
+                           int nproofs, const uint8_t* vp, size_t vp_len, const uint8_t* entropy32, uint8_t* out) {
+    return guard([&] {
+        if (!v || !nv || !proofs || !lens || !vp || !out) spx::invalid("null argument");
+        if (nproofs < 1) spx::invalid("nproofs must be at least 1");
+        for (int j = 0; j < nproofs; ++j)
+            if ((nv[j] && !v[j]) || (lens[j] && !proofs[j])) spx::invalid("null argument");
+        const auto r = spx::verify_many_coeffs(v, nv, proofs, lens, nproofs, vp, vp_len, entropy32);
+        memcpy(out, r.data(), r.size());
+    });
+}
+int spx_verify_stats(spx_ctx* ctx, uint64_t out[4]) {
+    return guard([&] {
+        if (!ctx || !out) spx::invalid("null argument");
+        for (int i = 0; i < 4; ++i) out[i] = ctx->c->vstat[i].load();
+    });
+}
 int spx_pairing_check(const uint8_t* g1, const uint8_t* g2, size_t n, int* is_one) {
     return guard([&] {
         if ((n && (!g1 || !g2)) || !is_one) spx::invalid("null argument");
@@ -769,6 +810,40 @@ int spx_msm_g2(spx_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_
         spx::CtxClaim claim(*ctx->c);
         auto r = spx::k_msm(*ctx->c, true, bases, scalars, n);
         memcpy(out192, r.data(), r.size());
+    });
+}
+int spx_g1_decompress(spx_ctx* ctx, const uint8_t* in, size_t n, uint8_t* out_uncompressed, uint8_t* ok) {
+    return guard([&] {
+        if (!in || !out_uncompressed || !ok) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_decompress(*ctx->c, false, in, n, out_uncompressed, ok);
+    });
+}
+int spx_g2_decompress(spx_ctx* ctx, const uint8_t* in, size_t n, uint8_t* out_uncompressed, uint8_t* ok) {
+    return guard([&] {
+        if (!in || !out_uncompressed || !ok) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_decompress(*ctx->c, true, in, n, out_uncompressed, ok);
+    });
+}
+int spx_lincomb_g1(spx_ctx* ctx, const uint8_t* bases_uncompressed, const uint8_t* scalars, size_t n,
+                   const uint64_t* seg_off, size_t nseg, uint8_t* out_uncompressed) {
+    return guard([&] {
+        if (!bases_uncompressed || !scalars || !seg_off || !out_uncompressed) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_lincomb(*ctx->c, false, bases_uncompressed, scalars, n, seg_off, nseg, out_uncompressed);
+    });
+}
+int spx_lincomb_g2(spx_ctx* ctx, const uint8_t* bases_uncompressed, const uint8_t* scalars, size_t n,
+                   const uint64_t* seg_off, size_t nseg, uint8_t* out_uncompressed) {
+    return guard([&] {
+        if (!bases_uncompressed || !scalars || !seg_off || !out_uncompressed) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_lincomb(*ctx->c, true, bases_uncompressed, scalars, n, seg_off, nseg, out_uncompressed);
     });
 }
 int spx_commit(spx_ctx* ctx, spx_pp* pp, const uint8_t* table, int nv, uint8_t* out56) {

@@ -331,4 +331,20 @@ void launch_points_to_canon_g2(G2Aff* pts, uint64_t n, hipStream_t s);
 void fixed_base_g1(const G1Aff* table, const Fr* scalars, uint64_t n, G1Aff* out, void* tmp, hipStream_t s);
 void fixed_base_g2(const G2Aff* table, const Fr* scalars, uint64_t n, G2Aff* out, void* tmp, hipStream_t s);
 
+// ---- verify_kernels.hip (the batch verifier)
+// n ark-serialize compressed points (48 / 96 bytes each, `in` 16-byte aligned) -> affine Montgomery with
+// the semantics of host::g1_decompress / g2_decompress (pairing.hpp). ok[j] = 1: accepted (infinity is
+// the (0, 0) sentinel); ok[j] = 0: non-canonical x or x^3 + b not a square (the sentinel is stored).
+void launch_decompress_g1(const uint8_t* in, uint64_t n, G1Aff* out, uint8_t* ok, hipStream_t s);
+void launch_decompress_g2(const uint8_t* in, uint64_t n, G2Aff* out, uint8_t* ok, hipStream_t s);
+// out[s] = sum_{seg_off[s] <= i < seg_off[s + 1]} k_i P_i (affine, (0, 0) = infinity) for n affine points
+// and n canonical scalars (plain integers below 2^256; the cost follows each scalar's bit length);
+// seg_off: nseg + 1 ascending device offsets ending at n. Sentinel points and zero scalars contribute
+// nothing. tmp: lincomb_tmp_bytes() of device scratch.
+size_t lincomb_tmp_bytes(bool g2, uint64_t n);
+void launch_lincomb_g1(const G1Aff* pts, const Fr* scalars, uint64_t n, const uint64_t* seg_off, uint32_t nseg,
+                       G1Aff* out, void* tmp, hipStream_t s);
+void launch_lincomb_g2(const G2Aff* pts, const Fr* scalars, uint64_t n, const uint64_t* seg_off, uint32_t nseg,
+                       G2Aff* out, void* tmp, hipStream_t s);
+
 }  // namespace spx

@@ -2165,6 +2165,9 @@ namespace {
 struct ProofReader {
     const uint8_t* b;
     size_t len, pos = 0;
+    // lazy: points stay bytes (spx_verify_many decompresses a whole batch's points on the GPU); the
+    // callers keep each point's offset
+    bool lazy = false;
     const uint8_t* take(size_t k) {
         if (pos + k > len) throw SpxError(kSerialization, "truncated proof");
         const uint8_t* p = b + pos;
@@ -2182,13 +2185,15 @@ struct ProofReader {
         return r;
     }
     host::Affine<HFq> g1() {
-        host::Affine<HFq> a;
-        if (!host::g1_decompress(a, take(48))) throw SpxError(kSerialization, "invalid G1 point");
+        host::Affine<HFq> a{HFq::zero(), HFq::zero(), false};
+        const uint8_t* p = take(48);
+        if (!lazy && !host::g1_decompress(a, p)) throw SpxError(kSerialization, "invalid G1 point");
         return a;
     }
     host::Affine<HFq2> g2() {
-        host::Affine<HFq2> a;
-        if (!host::g2_decompress(a, take(96))) throw SpxError(kSerialization, "invalid G2 point");
+        host::Affine<HFq2> a{HFq2::zero(), HFq2::zero(), false};
+        const uint8_t* p = take(96);
+        if (!lazy && !host::g2_decompress(a, p)) throw SpxError(kSerialization, "invalid G2 point");
         return a;
     }
 };
@@ -2196,14 +2201,20 @@ struct OpenProof {
     HFr eval;
     host::Affine<HFq2> h;
     std::vector<host::Affine<HFq2>> proofs;
+    size_t h_at = 0;             // byte offsets of the compressed points in the proof
+    std::vector<size_t> at;
 };
 OpenProof read_open(ProofReader& R) {
     OpenProof o;
     o.eval = R.fr();
+    o.h_at = R.pos;
     o.h = R.g2();
     const uint64_t k = R.u64();
     if (k > 64) throw SpxError(kSerialization, "bad opening proof length");
-    for (uint64_t i = 0; i < k; ++i) o.proofs.push_back(R.g2());
+    for (uint64_t i = 0; i < k; ++i) {
+        o.at.push_back(R.pos);
+        o.proofs.push_back(R.g2());
+    }
     return o;
 }
 std::vector<std::vector<HFr>> read_msgs(ProofReader& R, std::vector<std::pair<size_t, size_t>>& spans) {
@@ -2219,18 +2230,27 @@ std::vector<std::vector<HFr>> read_msgs(ProofReader& R, std::vector<std::pair<si
     }
     return m;
 }
-// linear-sumcheck interpolate_uni_poly: value at x of the polynomial through (i, ev[i])
-HFr interpolate(const std::vector<HFr>& ev, const HFr& x) {
+// linear-sumcheck interpolate_uni_poly: value at x of the polynomial through (i, ev[i]).
+// dinv[i] = 1 / prod_{j != i} (i - j): the same for every round of a sumcheck, so one batch inversion
+// serves them all (an inversion per term was most of the verifier's host arithmetic)
+std::vector<HFr> interpolation_weights(size_t n) {
+    std::vector<HFr> den(n, HFr::one());
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = 0; j < n; ++j)
+            if (j != i) den[i] = den[i] * (HFr::from_u64(i) - HFr::from_u64(j));
+    host::batch_inverse(den);
+    return den;
+}
+HFr interpolate(const std::vector<HFr>& ev, const HFr& x, const std::vector<HFr>& dinv) {
     const size_t n = ev.size();
     HFr total = HFr::zero();
     for (size_t i = 0; i < n; ++i) {
-        HFr num = HFr::one(), den = HFr::one();
+        HFr num = HFr::one();
         for (size_t j = 0; j < n; ++j) {
             if (j == i) continue;
             num = num * (x - HFr::from_u64(j));
-            den = den * (HFr::from_u64(i) - HFr::from_u64(j));
         }
-        total = total + ev[i] * num * den.inv();
+        total = total + ev[i] * num * dinv[i];
     }
     return total;
 }
@@ -2238,11 +2258,13 @@ HFr interpolate(const std::vector<HFr>& ev, const HFr& x) {
 HFr check_subclaim(const std::vector<std::vector<HFr>>& msgs, const std::vector<HFr>& rnd, HFr expected, int nv,
                    uint64_t max_mult) {
     if ((int)msgs.size() != nv) throw SpxError(kSumcheck, "insufficient rounds");
+    std::vector<HFr> dinv;
     for (size_t i = 0; i < msgs.size(); ++i) {
         if (msgs[i].size() != max_mult + 1) throw SpxError(kSumcheck, "wrong number of evaluations");
         if (!(msgs[i][0] + msgs[i][1] == expected))
             throw SpxError(kSumcheck, "Prover message is not consistent with the claim.");
-        expected = interpolate(msgs[i], rnd[i]);
+        if (dinv.empty()) dinv = interpolation_weights(msgs[i].size());
+        expected = interpolate(msgs[i], rnd[i], dinv);
     }
     return expected;
 }
@@ -2314,93 +2336,476 @@ static HFr eval_matrices_at(Ctx& C, Index& I, const std::vector<HFr>& r_x, const
     return ld_hfr(hp);
 }
 
-void verify(Ctx& C, Index& I, const uint8_t* v, size_t nv, const uint8_t* proof, size_t len, const VP& V,
-            const ProveOpts& o) {
-    if (I.G != 1) invalid("verify needs an index built on a single-rank context");
-    const int L = I.log_n;
-    const uint64_t n = I.n;
-    // verifier_init (verifier.rs:143-146)
+// ---- the pieces of the verifier, shared by verify() and verify_many()
+namespace {
+// verifier_init (verifier.rs:143-146)
+std::vector<HFr> parse_public(const uint8_t* v, size_t nv, uint64_t n) {
     if (!is_pow2(nv) || nv > n)
         invalid("public input should be power of two and has size smaller than number of constraints");
-    const int log_v = ilog2(nv);
     std::vector<HFr> vv(nv);
     for (size_t i = 0; i < nv; ++i)
         if (!host::fr_from_bytes(vv[i], v + 32 * i)) invalid("public input is not a canonical field element");
-    // parse (proof.rs:10-20 field order); remember each message's byte span for the transcript
-    ProofReader R{proof, len};
-    const size_t pm1_at = R.pos;
-    const uint64_t com_nv = R.u64();
-    const host::Affine<HFq> com = R.g1();
-    const size_t pm1_len = R.pos - pm1_at, pm2_at = R.pos;
-    const OpenProof op1 = read_open(R);
-    const size_t pm2_len = R.pos - pm2_at, pm3_at = R.pos;
-    const uint64_t mm1 = R.u64(), nv1 = R.u64();
+    return vv;
+}
+// a proof's fields (proof.rs:10-20 field order) with each message's byte span for the transcript
+struct ParsedProof {
+    size_t pm1_at, pm1_len, pm2_at, pm2_len, pm3_at, pm4_at, pm5_at, pm6_at, pm6_len, com_at;
+    uint64_t mm1, nv1, mm2, nv2;
+    host::Affine<HFq> com;
+    OpenProof op1, op2;
+    std::vector<std::vector<HFr>> sc1, sc2;
     std::vector<std::pair<size_t, size_t>> sp1, sp2;
-    const auto sc1 = read_msgs(R, sp1);
-    const size_t pm4_at = R.pos;
-    const HFr va = R.fr(), vb = R.fr(), vc = R.fr();
-    const size_t pm5_at = R.pos;
-    const uint64_t mm2 = R.u64(), nv2 = R.u64();
-    const auto sc2 = read_msgs(R, sp2);
-    const size_t pm6_at = R.pos;
-    const OpenProof op2 = read_open(R);
-    const size_t pm6_len = R.pos - pm6_at;
+    HFr va, vb, vc;
+};
+ParsedProof parse_proof(const uint8_t* proof, size_t len, bool lazy) {
+    ParsedProof P;
+    ProofReader R{proof, len};
+    R.lazy = lazy;
+    P.pm1_at = R.pos;
+    (void)R.u64();  // the commitment's nv
+    P.com_at = R.pos;
+    P.com = R.g1();
+    P.pm1_len = R.pos - P.pm1_at, P.pm2_at = R.pos;
+    P.op1 = read_open(R);
+    P.pm2_len = R.pos - P.pm2_at, P.pm3_at = R.pos;
+    P.mm1 = R.u64(), P.nv1 = R.u64();
+    P.sc1 = read_msgs(R, P.sp1);
+    P.pm4_at = R.pos;
+    P.va = R.fr(), P.vb = R.fr(), P.vc = R.fr();
+    P.pm5_at = R.pos;
+    P.mm2 = R.u64(), P.nv2 = R.u64();
+    P.sc2 = read_msgs(R, P.sp2);
+    P.pm6_at = R.pos;
+    P.op2 = read_open(R);
+    P.pm6_len = R.pos - P.pm6_at;
     if (R.pos != len) throw SpxError(kSerialization, "trailing bytes in proof");
-    (void)com_nv;
-    // transcript (lib.rs:152-212 feed order)
+    return P;
+}
+// the transcript state after A, B, C: the index cache, or a fresh absorption
+Blake2s matrices_state(const Index& I, const ProveOpts& o) {
+    if (o.cached && I.has_cache) return I.cache;
+    Blake2s h;
+    for (int m = 0; m < 3; ++m) feed_matrix(h, I.m[m]);
+    return h;
+}
+struct Challenges {
+    std::vector<HFr> r_v, tau, rand1, rand2;
+    HFr r_a, r_b, r_c;
+};
+// transcript replay (lib.rs:152-212 feed order) from the state after the matrices
+Challenges replay_transcript(const ParsedProof& P, const uint8_t* proof, const uint8_t* v, size_t nv, int L,
+                             const Blake2s& mats, const ProveOpts& o) {
+    Challenges c;
     Transcript T(o.mode == 1, o.seed);
-    if (o.cached && I.has_cache)
-        T.set_state(I.cache);
-    else {
-        Blake2s h;
-        for (int m = 0; m < 3; ++m) feed_matrix(h, I.m[m]);
-        T.set_state(h);
-    }
+    T.set_state(mats);
     {
         Ser s;
         s.u64(nv);
         s.raw(v, 32 * nv);
         T.feed(s.b.data(), s.b.size());
     }
-    T.feed(proof + pm1_at, pm1_len);
-    std::vector<HFr> r_v(log_v);
-    for (auto& r : r_v) r = T.rand_fr();
-    T.feed(proof + pm2_at, pm2_len);
-    std::vector<HFr> tau(L);
-    for (auto& t : tau) t = T.rand_fr();
-    if (nv1 != (uint64_t)L) invalid("invalid sumcheck proposal");
-    T.feed(proof + pm3_at, 16);
-    if ((int)sc1.size() != L || (int)sc2.size() != L) invalid("malformed sumcheck message");
-    std::vector<HFr> rand1, rand2;
-    for (auto& sp : sp1) {
+    T.feed(proof + P.pm1_at, P.pm1_len);
+    c.r_v.resize(ilog2(nv));
+    for (auto& r : c.r_v) r = T.rand_fr();
+    T.feed(proof + P.pm2_at, P.pm2_len);
+    c.tau.resize(L);
+    for (auto& t : c.tau) t = T.rand_fr();
+    if (P.nv1 != (uint64_t)L) invalid("invalid sumcheck proposal");
+    T.feed(proof + P.pm3_at, 16);
+    if ((int)P.sc1.size() != L || (int)P.sc2.size() != L) invalid("malformed sumcheck message");
+    for (auto& sp : P.sp1) {
         T.feed(proof + sp.first, sp.second);
-        rand1.push_back(T.rand_fr());
+        c.rand1.push_back(T.rand_fr());
     }
-    T.feed(proof + pm4_at, 96);
-    const HFr r_a = T.rand_fr(), r_b = T.rand_fr(), r_c = T.rand_fr();
-    if (nv2 != (uint64_t)L) invalid("invalid sumcheck proposal");
-    T.feed(proof + pm5_at, 16);
-    for (auto& sp : sp2) {
+    T.feed(proof + P.pm4_at, 96);
+    c.r_a = T.rand_fr(), c.r_b = T.rand_fr(), c.r_c = T.rand_fr();
+    if (P.nv2 != (uint64_t)L) invalid("invalid sumcheck proposal");
+    T.feed(proof + P.pm5_at, 16);
+    for (auto& sp : P.sp2) {
         T.feed(proof + sp.first, sp.second);
-        rand2.push_back(T.rand_fr());
+        c.rand2.push_back(T.rand_fr());
     }
-    T.feed(proof + pm6_at, pm6_len);
+    T.feed(proof + P.pm6_at, P.pm6_len);
+    return c;
+}
+// the first opening's point: r_v padded with zeros to L variables
+std::vector<HFr> padded_r_v(const Challenges& c, int L) {
+    std::vector<HFr> r(L, HFr::zero());
+    for (size_t i = 0; i < c.r_v.size(); ++i) r[i] = c.r_v[i];
+    return r;
+}
+// verify_sixth_round (verifier.rs:443-512) without its pairing checks and matrix evaluation: the
+// public-input MLE, both sumcheck subclaims and the eq(tau, r_x) product. Returns the second
+// sumcheck's subclaim, which (A, B, C)(r_x, r_y) z(r_y) must equal.
+HFr algebraic_checks(const ParsedProof& P, const Challenges& c, const std::vector<HFr>& vv, int L) {
+    if (!(mle_eval_host(vv, c.r_v) == P.op1.eval)) invalid("public witness is inconsistent with proof");
+    const HFr expected1 = check_subclaim(P.sc1, c.rand1, HFr::zero(), L, P.mm1);
+    HFr eq_rx = HFr::one();
+    for (int i = 0; i < L; ++i) eq_rx = eq_rx * eq1(c.tau[i], c.rand1[i]);
+    if (!((P.va * P.vb - P.vc) * eq_rx == expected1))
+        throw SpxError(kWrongWitness, "first sumcheck has wrong subclaim");
+    const HFr claimed2 = c.r_a * P.va + c.r_b * P.vb + c.r_c * P.vc;
+    return check_subclaim(P.sc2, c.rand2, claimed2, L, P.mm2);
+}
+}  // namespace
+
+void verify(Ctx& C, Index& I, const uint8_t* v, size_t nv, const uint8_t* proof, size_t len, const VP& V,
+            const ProveOpts& o) {
+    if (I.G != 1) invalid("verify needs an index built on a single-rank context");
+    const int L = I.log_n;
+    const std::vector<HFr> vv = parse_public(v, nv, I.n);
+    const ParsedProof P = parse_proof(proof, len, false);
+    const Challenges c = replay_transcript(P, proof, v, nv, L, matrices_state(I, o), o);
     // verify_sixth_round (verifier.rs:443-512)
     if (V.nv != L) invalid("verifier parameter nv != log_n");
-    std::vector<HFr> r_v0(L, HFr::zero());
-    for (int i = 0; i < log_v; ++i) r_v0[i] = r_v[i];
-    if (!mkzg_check(V, com, r_v0, op1.eval, op1)) invalid("public witness failed in commitment check");
-    if (!(mle_eval_host(vv, r_v) == op1.eval)) invalid("public witness is inconsistent with proof");
-    const HFr expected1 = check_subclaim(sc1, rand1, HFr::zero(), L, mm1);
-    HFr eq_rx = HFr::one();
-    for (int i = 0; i < L; ++i) eq_rx = eq_rx * eq1(tau[i], rand1[i]);
-    if (!((va * vb - vc) * eq_rx == expected1)) throw SpxError(kWrongWitness, "first sumcheck has wrong subclaim");
-    const HFr claimed2 = r_a * va + r_b * vb + r_c * vc;
-    const HFr expected2 = check_subclaim(sc2, rand2, claimed2, L, mm2);
-    const HFr rabc[3] = {r_a, r_b, r_c};
-    const HFr actual = eval_matrices_at(C, I, rand1, rabc, rand2) * op2.eval;
+    if (!mkzg_check(V, P.com, padded_r_v(c, L), P.op1.eval, P.op1)) invalid("public witness failed in commitment check");
+    const HFr expected2 = algebraic_checks(P, c, vv, L);
+    const HFr rabc[3] = {c.r_a, c.r_b, c.r_c};
+    const HFr actual = eval_matrices_at(C, I, c.rand1, rabc, c.rand2) * P.op2.eval;
     if (!(expected2 == actual)) throw SpxError(kWrongWitness, "Cannot verify matrix A, B, C");
-    if (!mkzg_check(V, com, rand2, op2.eval, op2)) throw SpxError(kWrongWitness, "Cannot verify z_ry");
+    if (!mkzg_check(V, P.com, c.rand2, P.op2.eval, P.op2)) throw SpxError(kWrongWitness, "Cannot verify z_ry");
+}
+
+// ====================================================================== batch verifier
+// spx_verify_many: the mKZG checks of every proof of a batch, all under one verifier
+// parameter, folded into one product of L + 2 pairings by a random linear combination.
+std::vector<uint8_t> verify_many_coeffs(const uint8_t* const* v, const size_t* nv, const uint8_t* const* proofs,
+                                        const size_t* lens, int k, const uint8_t* vp, size_t vp_len,
+                                        const uint8_t* entropy32) {
+    static const char tag[] = "spx-verify-many-v1";
+    static const uint8_t zeros[32] = {0};
+    Blake2s h;
+    h.update(tag, sizeof tag - 1);
+    h.update(vp, vp_len);
+    h.update(entropy32 ? entropy32 : zeros, 32);
+    for (int j = 0; j < k; ++j) {
+        const uint64_t a = nv[j], b = lens[j];
+        h.update(&a, 8);
+        h.update(v[j], 32 * nv[j]);
+        h.update(&b, 8);
+        h.update(proofs[j], lens[j]);
+    }
+    uint8_t seed[32];
+    h.peek(seed);
+    std::vector<uint8_t> out((size_t)64 * k, 0);
+    for (uint64_t i = 0; i < (uint64_t)2 * k; ++i) {
+        Blake2s g;
+        g.update(seed, 32);
+        g.update(&i, 8);
+        uint8_t d[32];
+        g.peek(d);
+        uint8_t* r = out.data() + 32 * i;
+        memcpy(r, d, 16);  // the low 128 bits
+        bool zero = true;
+        for (int t = 0; t < 16; ++t) zero &= r[t] == 0;
+        if (zero) r[0] = 1;
+    }
+    return out;
+}
+
+namespace {
+// one bump allocation over a device buffer and its pinned host mirror
+struct Mirror {
+    uint8_t *d, *h;
+    size_t pos = 0;
+    size_t take(size_t bytes) {
+        const size_t at = pos;
+        pos += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+};
+template <class F>
+host::Affine<F> aff_from_dev(const uint8_t* p) {  // device affine Montgomery ((0, 0) = infinity) -> host
+    host::Affine<F> a;
+    memcpy(&a.x, p, sizeof(F));
+    memcpy(&a.y, p + sizeof(F), sizeof(F));
+    a.inf = a.x.is_zero() && a.y.is_zero();
+    return a;
+}
+void fr_canon_to(uint8_t* out, const HFr& x) {
+    uint64_t c[4];
+    x.to_canon(c);
+    memcpy(out, c, 32);
+}
+}  // namespace
+
+void PinBuf::ensure(size_t b) {
+    if (b <= bytes) return;
+    if (p) (void)hipHostFree(p);
+    p = nullptr, bytes = 0;
+    SPX_HIP(hipHostMalloc(&p, b, hipHostMallocDefault));
+    bytes = b;
+}
+PinBuf::~PinBuf() {
+    if (p) (void)hipHostFree(p);
+}
+
+void verify_many(Ctx& C, Index& I, const uint8_t* const* v, const size_t* nv, const uint8_t* const* proofs,
+                 const size_t* lens, int k, const VP& V, const uint8_t* vp, size_t vp_len, const ProveOpts& o,
+                 const uint8_t* entropy32, std::vector<int>& status, std::vector<std::string>& msgs) {
+    if (I.G != 1) invalid("verify needs an index built on a single-rank context");
+    const int L = I.log_n;
+    status.assign(k, kOk);
+    msgs.assign(k, std::string());
+    struct Item {
+        bool live = true;
+        std::vector<HFr> vv;
+        ParsedProof P;
+        Challenges c;
+        HFr expected2;
+        HFr rho[2];
+    };
+    std::vector<Item> it(k);
+    // host wall time of the phases, for spx_last_timings: parse and replay, points queued and algebraic
+    // checks, the wait for the decompression, matrix evaluations, combinations, pairing, single-proof path
+    C.timings.clear();
+    Timer tph;
+    auto mark = [&](const char* name) {
+        C.timings.emplace_back(name, tph.us());
+        tph = Timer();
+    };
+    // (a) parse and replay; the matrices' transcript state once per call
+    {
+        Blake2s mats;
+        bool have = false;
+        for (int j = 0; j < k; ++j) {
+            Item& t = it[j];
+            try {
+                t.vv = parse_public(v[j], nv[j], I.n);
+                t.P = parse_proof(proofs[j], lens[j], true);
+                if (!have && o.mode != 1) mats = matrices_state(I, o);
+                have = true;
+                t.c = replay_transcript(t.P, proofs[j], v[j], nv[j], L, mats, o);
+                // the batch's shape: L quotient points per opening under a verifier parameter of L variables
+                if (V.nv != L || (int)t.P.op1.at.size() != L || (int)t.P.op2.at.size() != L) t.live = false;
+            } catch (const SpxError&) {
+                t.live = false;
+            }
+        }
+    }
+    mark("vm_parse_replay");
+    std::vector<int> batch;  // the proofs whose points go to the GPU
+    for (int j = 0; j < k; ++j)
+        if (it[j].live) batch.push_back(j);
+    const size_t nb = batch.size(), m = 2 * nb, n1 = nb, nq = (size_t)L * m, n2 = nq + m;
+    if (nb) {
+        // (d) first half: all points of the batch to the GPU, one launch per curve. G2 order: level i of
+        // opening o at i m + o (the A_i are segments, B is the whole run), then the openings' h points.
+        Mirror M{nullptr, nullptr};
+        const size_t cin1 = M.take(48 * n1), cin2 = M.take(96 * n2), okb = M.take(n1 + n2);
+        const size_t sc1 = M.take(32 * (n1 + 1)), scA = M.take(32 * nq), scB = M.take(32 * nq);
+        const size_t seg = M.take(8 * (L + 1 + 4)), gpt = M.take(96);
+        const size_t outs = M.take(192 * (L + 1) + 96);
+        const size_t mirrored = M.pos;
+        const size_t pts1 = M.take(96 * (n1 + 1)), pts2 = M.take(192 * n2);
+        const size_t tmp = M.take(std::max(lincomb_tmp_bytes(true, nq), lincomb_tmp_bytes(false, n1 + 1)));
+        C.vdev.ensure(M.pos);
+        C.vpin.ensure(mirrored);
+        M.d = C.vdev.as<uint8_t>();
+        M.h = static_cast<uint8_t*>(C.vpin.p);
+        for (size_t b = 0; b < nb; ++b) {
+            const int j = batch[b];
+            const ParsedProof& P = it[j].P;
+            memcpy(M.h + cin1 + 48 * b, proofs[j] + P.com_at, 48);
+            for (int op = 0; op < 2; ++op) {
+                const OpenProof& O = op ? P.op2 : P.op1;
+                const size_t oi = 2 * b + op;
+                for (int i = 0; i < L; ++i) memcpy(M.h + cin2 + 96 * ((size_t)i * m + oi), proofs[j] + O.at[i], 96);
+                memcpy(M.h + cin2 + 96 * (nq + oi), proofs[j] + O.h_at, 96);
+            }
+        }
+        SPX_HIP(hipMemcpyAsync(M.d + cin1, M.h + cin1, cin2 + 96 * n2 - cin1, hipMemcpyHostToDevice, C.stream));
+        launch_decompress_g1(M.d + cin1, n1, reinterpret_cast<G1Aff*>(M.d + pts1), M.d + okb, C.stream);
+        launch_decompress_g2(M.d + cin2, n2, reinterpret_cast<G2Aff*>(M.d + pts2), M.d + okb + n1, C.stream);
+        SPX_HIP(hipMemcpyAsync(M.h + okb, M.d + okb, n1 + n2, hipMemcpyDeviceToHost, C.stream));
+        C.vstat[3] += n1 + n2;
+        // (b) the algebraic checks, on the host while the points decompress
+        for (int j : batch) {
+            try {
+                it[j].expected2 = algebraic_checks(it[j].P, it[j].c, it[j].vv, L);
+            } catch (const SpxError&) {
+                it[j].live = false;
+            }
+        }
+        mark("vm_algebra");
+        C.sync();
+        for (size_t b = 0; b < nb; ++b) {
+            bool ok = M.h[okb + b] != 0;
+            for (int op = 0; op < 2; ++op) {
+                const size_t oi = 2 * b + op;
+                for (int i = 0; i <= L; ++i) ok &= M.h[okb + n1 + (size_t)i * m + oi] != 0;
+            }
+            if (!ok) it[batch[b]].live = false;
+        }
+        mark("vm_points_wait");
+        // (c) the matrix evaluations
+        for (int j : batch) {
+            if (!it[j].live) continue;
+            const Challenges& c = it[j].c;
+            const HFr rabc[3] = {c.r_a, c.r_b, c.r_c};
+            const HFr actual = eval_matrices_at(C, I, c.rand1, rabc, c.rand2) * it[j].P.op2.eval;
+            if (!(it[j].expected2 == actual)) it[j].live = false;
+        }
+        mark("vm_matrix_eval");
+        // (d) second half: the combinations. A proof that left the batch keeps its slots with zero scalars.
+        const std::vector<uint8_t> rho = verify_many_coeffs(v, nv, proofs, lens, k, vp, vp_len, entropy32);
+        size_t nlive = 0;
+        HFr vsum = HFr::zero();
+        memset(M.h + sc1, 0, scB + 32 * nq - sc1);
+        for (size_t b = 0; b < nb; ++b) {
+            Item& t = it[batch[b]];
+            if (!t.live) continue;
+            ++nlive;
+            for (int op = 0; op < 2; ++op) {
+                uint64_t c4[4] = {0, 0, 0, 0};
+                memcpy(c4, rho.data() + 32 * (2 * (size_t)batch[b] + op), 16);
+                t.rho[op] = HFr::from_canon(c4);
+                const OpenProof& O = op ? t.P.op2 : t.P.op1;
+                vsum = vsum + t.rho[op] * O.eval;
+                const std::vector<HFr> z = op ? t.c.rand2 : padded_r_v(t.c, L);
+                const size_t oi = 2 * b + op;
+                for (int i = 0; i < L; ++i) {
+                    memcpy(M.h + scA + 32 * ((size_t)i * m + oi), c4, 32);
+                    fr_canon_to(M.h + scB + 32 * ((size_t)i * m + oi), t.rho[op] * z[i]);
+                }
+            }
+            fr_canon_to(M.h + sc1 + 32 * b, t.rho[0] + t.rho[1]);
+        }
+        if (nlive) {
+            fr_canon_to(M.h + sc1 + 32 * n1, HFr::zero() - vsum);
+            uint64_t* so = reinterpret_cast<uint64_t*>(M.h + seg);
+            for (int i = 0; i <= L; ++i) so[i] = (uint64_t)i * m;  // the A_i
+            so[L + 1] = 0, so[L + 2] = nq;                         // B
+            so[L + 3] = 0, so[L + 4] = n1 + 1;                     // C
+            memset(M.h + gpt, 0, 96);
+            if (!V.g.inf) {
+                memcpy(M.h + gpt, &V.g.x, 48);
+                memcpy(M.h + gpt + 48, &V.g.y, 48);
+            }
+            SPX_HIP(hipMemcpyAsync(M.d + sc1, M.h + sc1, gpt + 96 - sc1, hipMemcpyHostToDevice, C.stream));
+            SPX_HIP(hipMemcpyAsync(M.d + pts1 + 96 * n1, M.d + gpt, 96, hipMemcpyDeviceToDevice, C.stream));
+            const uint64_t* dso = reinterpret_cast<const uint64_t*>(M.d + seg);
+            G2Aff* outA = reinterpret_cast<G2Aff*>(M.d + outs);
+            G1Aff* outC = reinterpret_cast<G1Aff*>(M.d + outs + 192 * (L + 1));
+            launch_lincomb_g2(reinterpret_cast<const G2Aff*>(M.d + pts2), reinterpret_cast<const Fr*>(M.d + scA), nq, dso,
+                              (uint32_t)L, outA, M.d + tmp, C.stream);
+            launch_lincomb_g2(reinterpret_cast<const G2Aff*>(M.d + pts2), reinterpret_cast<const Fr*>(M.d + scB), nq,
+                              dso + L + 1, 1, outA + L, M.d + tmp, C.stream);
+            launch_lincomb_g1(reinterpret_cast<const G1Aff*>(M.d + pts1), reinterpret_cast<const Fr*>(M.d + sc1), n1 + 1,
+                              dso + L + 3, 1, outC, M.d + tmp, C.stream);
+            SPX_HIP(hipMemcpyAsync(M.h + outs, M.d + outs, 192 * (L + 1) + 96, hipMemcpyDeviceToHost, C.stream));
+            C.sync();
+            mark("vm_combine");
+            // e(C, h) e(g, B) prod_i e(-g_mask_i, A_i) == 1
+            std::vector<std::pair<host::Affine<HFq>, host::Affine<HFq2>>> pairs;
+            pairs.push_back({aff_from_dev<HFq>(M.h + outs + 192 * (L + 1)), V.h});
+            pairs.push_back({V.g, aff_from_dev<HFq2>(M.h + outs + 192 * L)});
+            for (int i = 0; i < L; ++i) {
+                host::Affine<HFq> gm = V.g_mask[i];
+                if (!gm.inf) gm.y = -gm.y;
+                pairs.push_back({gm, aff_from_dev<HFq2>(M.h + outs + 192 * i)});
+            }
+            C.vstat[0] += 1;
+            C.vstat[1] += pairs.size();
+            bool one = false;
+            try {
+                one = host::pairing_product_is_one(pairs);
+            } catch (const std::runtime_error&) {  // a degenerate Miller step: settle each proof alone
+                one = false;
+            }
+            if (!one)
+                for (int j : batch) it[j].live = false;
+            mark("vm_pairing");
+        }
+    }
+    // every proof that left the fast path takes the single-proof path, which names its error
+    tph = Timer();
+    for (int j = 0; j < k; ++j) {
+        if (it[j].live) continue;
+        C.vstat[2] += 1;
+        try {
+            verify(C, I, v[j], nv[j], proofs[j], lens[j], V, o);
+        } catch (const SpxError& e) {
+            status[j] = e.code;
+            msgs[j] = e.what();
+        } catch (const std::bad_alloc&) {
+            throw;
+        } catch (const std::exception& e) {
+            status[j] = kDevice;
+            msgs[j] = e.what();
+        }
+    }
+    while (C.timings.size() < 6) C.timings.emplace_back("vm_not_run", 0.0);  // fixed positions
+    mark("vm_single_path");
+}
+
+// ---- kernel-level entries of the batch verifier's kernels (parity tests)
+void k_decompress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok) {
+    if (n == 0) invalid("no points");
+    const size_t cs = g2 ? 96 : 48, ps = 2 * cs;
+    DevMem din(cs * n), pts(ps * n), dok(n);
+    SPX_HIP(hipMemcpyAsync(din.p, in, cs * n, hipMemcpyHostToDevice, C.stream));
+    if (g2) {
+        launch_decompress_g2(din.as<uint8_t>(), n, pts.as<G2Aff>(), dok.as<uint8_t>(), C.stream);
+        launch_points_to_canon_g2(pts.as<G2Aff>(), n, C.stream);
+    } else {
+        launch_decompress_g1(din.as<uint8_t>(), n, pts.as<G1Aff>(), dok.as<uint8_t>(), C.stream);
+        launch_points_to_canon_g1(pts.as<G1Aff>(), n, C.stream);
+    }
+    SPX_HIP(hipMemcpyAsync(out, pts.p, ps * n, hipMemcpyDeviceToHost, C.stream));
+    SPX_HIP(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    for (size_t j = 0; j < n; ++j) {  // infinity carries the ark flag; a rejected point stays all zero
+        uint8_t* p = out + ps * j;
+        bool zero = true;
+        for (size_t t = 0; t < ps; ++t) zero &= p[t] == 0;
+        if (zero && ok[j]) {
+            p[cs] = 1;  // y = 1
+            p[ps - 1] |= host::kFlagInf;
+        }
+    }
+}
+void k_lincomb(Ctx& C, bool g2, const uint8_t* bases, const uint8_t* scalars, size_t n, const uint64_t* seg_off,
+               size_t nseg, uint8_t* out) {
+    if (n == 0 || nseg == 0) invalid("empty linear combination");
+    if (seg_off[0] != 0 || seg_off[nseg] != n) invalid("segment offsets must run from 0 to n");
+    for (size_t s = 0; s < nseg; ++s)
+        if (seg_off[s] > seg_off[s + 1]) invalid("segment offsets must ascend");
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t c[4];
+        memcpy(c, scalars + 32 * i, 32);
+        if (HFr::geq_p(c)) throw SpxError(kSerialization, "non-canonical scalar");
+    }
+    const size_t ps = g2 ? 192 : 96;
+    DevMem raw(ps * n), sc(32 * n), so(8 * (nseg + 1)), res(ps * nseg), tmp(lincomb_tmp_bytes(g2, n)), err(sizeof(int));
+    SPX_HIP(hipMemsetAsync(err.p, 0, 4, C.stream));
+    SPX_HIP(hipMemcpyAsync(raw.p, bases, ps * n, hipMemcpyHostToDevice, C.stream));
+    SPX_HIP(hipMemcpyAsync(sc.p, scalars, 32 * n, hipMemcpyHostToDevice, C.stream));
+    SPX_HIP(hipMemcpyAsync(so.p, seg_off, 8 * (nseg + 1), hipMemcpyHostToDevice, C.stream));
+    if (g2) {
+        launch_points_from_bytes_g2(raw.as<G2Aff>(), n, err.as<int>(), C.stream);
+        launch_lincomb_g2(raw.as<G2Aff>(), sc.as<Fr>(), n, so.as<uint64_t>(), (uint32_t)nseg, res.as<G2Aff>(), tmp.p, C.stream);
+        launch_points_to_canon_g2(res.as<G2Aff>(), nseg, C.stream);
+    } else {
+        launch_points_from_bytes_g1(raw.as<G1Aff>(), n, err.as<int>(), C.stream);
+        launch_lincomb_g1(raw.as<G1Aff>(), sc.as<Fr>(), n, so.as<uint64_t>(), (uint32_t)nseg, res.as<G1Aff>(), tmp.p, C.stream);
+        launch_points_to_canon_g1(res.as<G1Aff>(), nseg, C.stream);
+    }
+    int herr = 0;
+    SPX_HIP(hipMemcpyAsync(out, res.p, ps * nseg, hipMemcpyDeviceToHost, C.stream));
+    SPX_HIP(hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    if (herr & 1) throw SpxError(kSerialization, "non-canonical input");
+    if (herr & 2) throw SpxError(kSerialization, "base point not on the curve");
+    for (size_t s = 0; s < nseg; ++s) {
+        uint8_t* p = out + ps * s;
+        bool zero = true;
+        for (size_t t = 0; t < ps; ++t) zero &= p[t] == 0;
+        if (zero) {
+            p[ps / 2] = 1;
+            p[ps - 1] |= host::kFlagInf;
+        }
+    }
 }
 
 static HostCsr single(const HostCsr& m) { return m; }

@@ -84,6 +84,17 @@ struct DevMem {
     DevMem& operator=(const DevMem&) = delete;
 };
 
+// grow-only pinned host allocation (async copies need pinned memory that outlives the covering sync)
+struct PinBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    void ensure(size_t b);
+    ~PinBuf();
+};
+
 // ---------------------------------------------------------------- communicators
 struct Comm {
     virtual ~Comm() {}
@@ -230,6 +241,13 @@ struct Ctx {
     // one prove or round-level session at a time: both own the streams, the scratch tables, the pinned
     // carve-out and the sumcheck ticket (CtxClaim)
     std::atomic<bool> in_use{false};
+    // the batch verifier (verify_many): its device buffer with the pinned host mirror of the part that
+    // is copied (grow-only, reused only after the sync that covers a batch's copies), and its counters:
+    // batches run, pairs given to the Miller loop by the batched path, proofs sent to the single-proof
+    // path, points decompressed on the GPU
+    DevMem vdev;
+    PinBuf vpin;
+    std::atomic<uint64_t> vstat[4] = {};
     Ctx(int dev);
     ~Ctx();
     // region [off, off + bytes) of the pinned carve-out (throws if it does not fit its region)
@@ -420,6 +438,24 @@ VP vp_from_pp(const PP& P);  // keygen-generated PP only (keeps the trapdoor)
 // reference's Err(...); returns normally on acceptance (Ok(true))
 void verify(Ctx& C, Index& I, const uint8_t* v, size_t nv, const uint8_t* proof, size_t len, const VP& V,
             const ProveOpts& o);
+
+// k proofs of one index under one verifier parameter (vp: V's bytes, hashed into the coefficients):
+// status[j] / msgs[j] = what verify() gives for proof j alone (kOk and an empty message on acceptance).
+// Valid proofs share one product of L + 2 pairings; a proof that fails anything on the way,
+// and every proof of a batch whose combined check fails, is settled by verify(). Throws only for errors
+// of the call itself.
+void verify_many(Ctx& C, Index& I, const uint8_t* const* v, const size_t* nv, const uint8_t* const* proofs,
+                 const size_t* lens, int k, const VP& V, const uint8_t* vp, size_t vp_len, const ProveOpts& o,
+                 const uint8_t* entropy32, std::vector<int>& status, std::vector<std::string>& msgs);
+// the 2 k coefficients rho_{j,o} of verify_many as 32-byte canonical Fr (host only)
+std::vector<uint8_t> verify_many_coeffs(const uint8_t* const* v, const size_t* nv, const uint8_t* const* proofs,
+                                        const size_t* lens, int k, const uint8_t* vp, size_t vp_len,
+                                        const uint8_t* entropy32);
+// n compressed points -> uncompressed ark bytes (infinity flagged; all zero where ok[j] = 0)
+void k_decompress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok);
+// out[s] = sum over segment s of scalar_i base_i; uncompressed ark bytes in and out
+void k_lincomb(Ctx& C, bool g2, const uint8_t* bases, const uint8_t* scalars, size_t n, const uint64_t* seg_off,
+               size_t nseg, uint8_t* out);
 
 std::vector<uint8_t> k_sum_over_y(Ctx& C, const HostCsr& m, const uint8_t* z);
 std::vector<uint8_t> k_eval_on_x(Ctx& C, const HostCsr& m, const uint8_t* r_x);
