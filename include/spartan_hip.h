@@ -382,6 +382,43 @@ int spx_lincomb_g1(spx_ctx *ctx, const uint8_t *bases_uncompressed, const uint8_
                    const uint64_t *seg_off, size_t nseg, uint8_t *out_uncompressed);
 int spx_lincomb_g2(spx_ctx *ctx, const uint8_t *bases_uncompressed, const uint8_t *scalars, size_t n,
                    const uint64_t *seg_off, size_t nseg, uint8_t *out_uncompressed);
+/* ---- subgroup membership ("Subgroup membership") ----
+ * Membership of the prime-order subgroups G1 / G2 by the fixed-scalar endomorphism tests (phi(P) = -[z^2] P
+ * on G1, psi(P) = [z] P on G2), which is what arkworks' checked deserialization adds to the canonical-
+ * encoding and on-curve checks that every entry point of this library makes. Everything here is opt-in:
+ * with nothing set, spx_pp_load, spx_verify and spx_verify_many behave as before.
+ *
+ * spx_g1_in_subgroup / spx_g2_in_subgroup: n uncompressed points (96 / 192 B each) tested on the ctx's
+ * GPU. ok[j] = 1 for a member (infinity included), 0 for a non-member, a non-canonical coordinate or a
+ * point off the curve. */
+int spx_g1_in_subgroup(spx_ctx *ctx, const uint8_t *pts_uncompressed, size_t n, uint8_t *ok);
+int spx_g2_in_subgroup(spx_ctx *ctx, const uint8_t *pts_uncompressed, size_t n, uint8_t *ok);
+/* the same test of one point (curve 1: G1, 96 B; 2: G2, 192 B) on the host; no GPU. A caller can check
+ * the points of a verifier parameter with it: spx_verify / spx_verify_many trust vp and never check it. */
+int spx_point_in_subgroup_host(int curve /* 1 | 2 */, const uint8_t *pt_uncompressed, int *ok);
+/* Checks every raw G1 and G2 level of a loaded or generated public parameter on the ctx's GPU, and g and
+ * h on the host (spx_pp_load itself does not: the check is load time a trusted file does not need).
+ * SPX_OK with *bad = 0, or SPX_SERIALIZATION with *bad = the number of points outside their subgroup and
+ * spx_last_error naming the first one. first = {curve (1 | 2), level (UINT64_MAX for g / h), index} of
+ * the lowest offender in the order G1 levels, G2 levels, g, h: the same whatever order the GPU ran in.
+ * bad and first may each be NULL. Every rank of a sharded context holds the complete raw levels, so the
+ * call works on any context of the public parameter's device. */
+int spx_pp_check_subgroup(spx_ctx *ctx, spx_pp *pp, uint64_t *bad, uint64_t first[3]);
+/* Subgroup check of proof points in spx_verify and spx_verify_many on this context: 0 = off (the
+ * default: every status and message as before), 1 = on, -1 = the process default (SPX_SUBGROUP_CHECK=1
+ * -> on, else off). On: spx_verify tests the commitment and every point of the two opening proofs right
+ * after decompressing it, before any transcript replay or algebraic check, and a non-member fails with
+ * SPX_SERIALIZATION and a message naming the field ("commitment", "opening 1 h", "opening 2 proof point
+ * 3": "... is not in the prime-order subgroup"), as Proof::deserialize does in the reference
+ * (/root/reference/src/benchmark.rs:45). spx_verify_many tests a batch's points on the GPU behind their
+ * decompression; a proof with a rejected point goes to the single-proof path, and status[j] is still what
+ * spx_verify gives for proof j on a context with the same setting. vp is not checked.
+ * SPX_INVALID_ARGUMENT while the context is in use. */
+int spx_ctx_set_subgroup_check(spx_ctx *ctx, int mode);
+/* membership checks made through this context, cumulative: out[0] points checked on the GPU, out[1] points
+ * checked on the host, out[2] points rejected as reported to the caller (ok = 0, a public parameter's
+ * offenders, a strict spx_verify's error; a batch's rejected point counts once, on the single-proof path) */
+int spx_subgroup_stats(spx_ctx *ctx, uint64_t out[3]);
 int spx_commit(spx_ctx *ctx, spx_pp *pp, const uint8_t *table, int nv, uint8_t *out56);
 /* proof_out: Proof{h, proofs} compressed = 96 + 8 + 96 * nv bytes */
 int spx_open(spx_ctx *ctx, spx_pp *pp, const uint8_t *table, int nv, const uint8_t *point, uint8_t *eval_out,

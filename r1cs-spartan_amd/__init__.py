@@ -151,6 +151,12 @@ EXPORTED = [
     "spx_g2_decompress",
     "spx_lincomb_g1",
     "spx_lincomb_g2",
+    "spx_g1_in_subgroup",
+    "spx_g2_in_subgroup",
+    "spx_point_in_subgroup_host",
+    "spx_pp_check_subgroup",
+    "spx_ctx_set_subgroup_check",
+    "spx_subgroup_stats",
     "spx_commit",
     "spx_open",
 ]
@@ -238,6 +244,14 @@ def lib():
         L.spx_g2_decompress.argtypes = [vp, u8p, sz, ctypes.c_void_p, ctypes.c_void_p]
         L.spx_lincomb_g1.argtypes = [vp, u8p, u8p, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_void_p]
         L.spx_lincomb_g2.argtypes = [vp, u8p, u8p, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_void_p]
+    if hasattr(L, "spx_g1_in_subgroup") or not os.environ.get("SPX_LIB_PATH"):  # A/B builds may predate it
+        pu64 = ctypes.POINTER(ctypes.c_uint64)
+        L.spx_g1_in_subgroup.argtypes = [vp, u8p, sz, ctypes.c_void_p]
+        L.spx_g2_in_subgroup.argtypes = [vp, u8p, sz, ctypes.c_void_p]
+        L.spx_point_in_subgroup_host.argtypes = [ctypes.c_int, u8p, ctypes.POINTER(ctypes.c_int)]
+        L.spx_pp_check_subgroup.argtypes = [vp, vp, pu64, pu64]
+        L.spx_ctx_set_subgroup_check.argtypes = [vp, ctypes.c_int]
+        L.spx_subgroup_stats.argtypes = [vp, pu64]
     if hasattr(L, "spx_hash_stats") or not os.environ.get("SPX_LIB_PATH"):
         L.spx_hash_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.spx_vp_from_pp.argtypes = [vp, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
@@ -380,6 +394,18 @@ class Context:
         default), 0 off (listed and counted only: A/B), -1 the process default (SPX_MSM_HOT); no effect
         on the proof bytes (spx_ctx_set_msm_hot)"""
         _check(lib().spx_ctx_set_msm_hot(self.h, int(mode)))
+
+    def set_subgroup_check(self, mode):
+        """subgroup check of proof points in verify / verify_many on this context: 1 on, 0 off (the
+        default), -1 the process default (SPX_SUBGROUP_CHECK=1 -> on; spx_ctx_set_subgroup_check)"""
+        _check(lib().spx_ctx_set_subgroup_check(self.h, int(mode)))
+
+    def subgroup_stats(self):
+        """(points checked on the GPU, points checked on the host, points rejected) by the membership
+        checks made through this context, cumulative (spx_subgroup_stats)"""
+        v = (ctypes.c_uint64 * 3)()
+        _check(lib().spx_subgroup_stats(self.h, v))
+        return tuple(int(x) for x in v)
 
     def msm_skew_stats(self):
         """(MSM batches run, batches with a hot bucket, hot buckets reduced, most partials the weighting
@@ -590,10 +616,29 @@ class PublicParameter:
         self.ctx, self.h, self.nv = ctx, h, nv
 
     @staticmethod
-    def load(ctx, data):
+    def load(ctx, data, check_subgroup=False):
+        """check_subgroup: also test every point for membership of its prime-order subgroup
+        (spx_pp_check_subgroup) and raise SerializationError naming the first one outside it"""
         h = ctypes.c_void_p()
         _check(lib().spx_pp_load(ctx.h, bytes(data), len(data), ctypes.byref(h)))
-        return PublicParameter(ctx, h, int.from_bytes(data[:8], "little"))
+        pp = PublicParameter(ctx, h, int.from_bytes(data[:8], "little"))
+        if check_subgroup:
+            pp.check_subgroup()
+        return pp
+
+    def check_subgroup(self, strict=True):
+        """Membership of every G1 and G2 point (the raw levels on the GPU, g and h on the host;
+        spx_pp_check_subgroup). Returns (bad, first): the number of points outside their subgroup and the
+        lowest one as (curve, level or None for g / h, index), or None. strict: raise SerializationError
+        when bad > 0 instead of returning."""
+        bad = ctypes.c_uint64(0)
+        first = (ctypes.c_uint64 * 3)()
+        rc = lib().spx_pp_check_subgroup(self.ctx.h, self.h, ctypes.byref(bad), first)
+        if rc != 0 and (strict or rc != 4):
+            _check(rc)
+        if bad.value == 0:
+            return 0, None
+        return bad.value, (int(first[0]), None if first[1] == 2**64 - 1 else int(first[1]), int(first[2]))
 
     def window_plan(self, level):
         """(window bits, windows) of the commitment MSM (level -1) or of opening level 0 .. nv - 1
@@ -993,6 +1038,41 @@ def g1_decompress(ctx, compressed):
 
 def g2_decompress(ctx, compressed):
     return _decompress(lib().spx_g2_decompress, ctx, compressed, 96)
+
+
+# One launch of the membership kernels covers this many points; a longer array takes a second pass of
+# its grid-stride loop (kSubgroupMaxBlocks x kSubgroupLanes, kernels.hpp)
+SUBGROUP_GRID_POINTS = 4096 * 64
+
+
+def _in_subgroup(fn, ctx, pts, ps):
+    pts = bytes(pts)
+    if not pts or len(pts) % ps:
+        raise InvalidArgument("uncompressed points are %d bytes each" % ps)
+    n = len(pts) // ps
+    ok = ctypes.create_string_buffer(n)
+    _check(fn(ctx.h, pts, n, ok))
+    return [b != 0 for b in ok.raw]
+
+
+def g1_in_subgroup(ctx, pts_uncompressed):
+    """[point j is canonical, on the curve and in G1 (infinity included)] for concatenated 96-byte
+    uncompressed points; the membership test runs on the GPU (spx_g1_in_subgroup)"""
+    return _in_subgroup(lib().spx_g1_in_subgroup, ctx, pts_uncompressed, 96)
+
+
+def g2_in_subgroup(ctx, pts_uncompressed):
+    return _in_subgroup(lib().spx_g2_in_subgroup, ctx, pts_uncompressed, 192)
+
+
+def point_in_subgroup_host(curve, pt_uncompressed):
+    """the same test of one point (curve 1: G1, 2: G2) on the host, no GPU (spx_point_in_subgroup_host)"""
+    pt = bytes(pt_uncompressed)
+    if curve not in (1, 2) or len(pt) != 96 * curve:
+        raise InvalidArgument("curve 1: one 96-byte point, curve 2: one 192-byte point")
+    ok = ctypes.c_int(0)
+    _check(lib().spx_point_in_subgroup_host(int(curve), pt, ctypes.byref(ok)))
+    return ok.value == 1
 
 
 def _lincomb(fn, ctx, bases, scalars, seg_off, ps):

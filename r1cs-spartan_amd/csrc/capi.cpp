@@ -846,6 +846,66 @@ int spx_lincomb_g2(spx_ctx* ctx, const uint8_t* bases_uncompressed, const uint8_
         spx::k_lincomb(*ctx->c, true, bases_uncompressed, scalars, n, seg_off, nseg, out_uncompressed);
     });
 }
+// ---- subgroup membership
+int spx_g1_in_subgroup(spx_ctx* ctx, const uint8_t* pts_uncompressed, size_t n, uint8_t* ok) {
+    return guard([&] {
+        if (!pts_uncompressed || !ok) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_in_subgroup(*ctx->c, false, pts_uncompressed, n, ok);
+    });
+}
+int spx_g2_in_subgroup(spx_ctx* ctx, const uint8_t* pts_uncompressed, size_t n, uint8_t* ok) {
+    return guard([&] {
+        if (!pts_uncompressed || !ok) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_in_subgroup(*ctx->c, true, pts_uncompressed, n, ok);
+    });
+}
+int spx_point_in_subgroup_host(int curve, const uint8_t* pt_uncompressed, int* ok) {
+    return guard([&] {
+        if (!pt_uncompressed || !ok) spx::invalid("null argument");
+        if (curve == 1) {
+            spx::host::Affine<spx::host::Fq> a;
+            *ok = spx::host::g1_from_uncompressed(a, pt_uncompressed) && spx::host::on_curve(a) &&
+                  spx::host::g1_in_subgroup(a);
+        } else if (curve == 2) {
+            spx::host::Affine<spx::host::Fq2> a;
+            *ok = spx::host::g2_from_uncompressed(a, pt_uncompressed) && spx::host::on_curve(a) &&
+                  spx::host::g2_in_subgroup(a);
+        } else {
+            spx::invalid("curve must be 1 (G1) or 2 (G2)");
+        }
+    });
+}
+int spx_pp_check_subgroup(spx_ctx* ctx, spx_pp* pp, uint64_t* bad, uint64_t first[3]) {
+    return guard([&] {
+        if (!pp) spx::invalid("null public parameter");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        const spx::PPSubgroupReport r = spx::pp_check_subgroup(*ctx->c, *pp->p);
+        if (bad) *bad = r.bad;
+        if (first)
+            for (int i = 0; i < 3; ++i) first[i] = r.first[i];
+        if (r.bad) throw spx::SpxError(spx::kSerialization, r.message);
+    });
+}
+int spx_ctx_set_subgroup_check(spx_ctx* ctx, int mode) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (mode < -1 || mode > 1) spx::invalid("subgroup check mode must be -1, 0 or 1");
+        if (ctx->c->in_use.load()) spx::invalid("context in use by a prove or session");
+        ctx->c->subgroup_mode = mode;
+    });
+}
+int spx_subgroup_stats(spx_ctx* ctx, uint64_t out[3]) {
+    return guard([&] {
+        if (!ctx || !out) spx::invalid("null argument");
+        for (int i = 0; i < 3; ++i) out[i] = ctx->c->sgstat[i].load();
+    });
+}
+
 int spx_commit(spx_ctx* ctx, spx_pp* pp, const uint8_t* table, int nv, uint8_t* out56) {
     return guard([&] {
         set_dev(ctx);

@@ -10,6 +10,8 @@
 #include <stdexcept>
 #include <vector>
 
+#include "subgroup_consts.hpp"
+
 namespace spx {
 namespace host {
 
@@ -415,6 +417,45 @@ inline Affine<Fq2> g2_generator() {
     memcpy(a.y.c1.v, Y1, 48);
     a.inf = false;
     return a;
+}
+
+// ---------------------------------------------------------------- subgroup membership
+// The fixed-scalar endomorphism tests ("Subgroup membership"; constants from
+// tools/gen_subgroup_consts.py). The input is on the curve; infinity is a member.
+inline Fq sg_const(const uint64_t (&m)[6]) {
+    Fq r;
+    memcpy(r.v, m, 48);
+    return r;
+}
+// [|z|] p: 63 doublings and 5 additions
+template <class F>
+inline Jac<F> jac_mul_z_abs(const Jac<F>& p) {
+    Jac<F> acc = p;
+    for (int b = 62; b >= 0; --b) {
+        acc = jac_dbl(acc);
+        if ((kSgZAbs >> b) & 1) acc = jac_add(acc, p);
+    }
+    return acc;
+}
+// (ex, ey) == -t without an inversion: ex Z^2 = X and ey Z^3 = -Y
+template <class F>
+inline bool sg_is_neg_of(const F& ex, const F& ey, const Jac<F>& t) {
+    if (t.z.is_zero()) return false;  // the input is finite
+    const F z2 = t.z * t.z, z3 = z2 * t.z;
+    return ex * z2 == t.x && ey * z3 == -t.y;
+}
+// phi(P) = (beta x, y) = -[z^2] P
+inline bool g1_in_subgroup(const Affine<Fq>& a) {
+    if (a.inf) return true;
+    const Jac<Fq> t = jac_mul_z_abs(jac_mul_z_abs(jac_from(a)));
+    return sg_is_neg_of(sg_const(kSgBeta) * a.x, a.y, t);
+}
+// psi(P) = (conj(x) c_x, conj(y) c_y) = [z] P = -[|z|] P
+inline bool g2_in_subgroup(const Affine<Fq2>& a) {
+    if (a.inf) return true;
+    const Fq2 cx = {sg_const(kSgPsiX0), sg_const(kSgPsiX1)}, cy = {sg_const(kSgPsiY0), sg_const(kSgPsiY1)};
+    const Fq2 xb = {a.x.c0, -a.x.c1}, yb = {a.y.c0, -a.y.c1};
+    return sg_is_neg_of(xb * cx, yb * cy, jac_mul_z_abs(jac_from(a)));
 }
 
 // batch inversion (Montgomery's trick); zeros stay zero

@@ -347,4 +347,14 @@ void launch_lincomb_g1(const G1Aff* pts, const Fr* scalars, uint64_t n, const ui
 void launch_lincomb_g2(const G2Aff* pts, const Fr* scalars, uint64_t n, const uint64_t* seg_off, uint32_t nseg,
                        G2Aff* out, void* tmp, hipStream_t s);
 
+// ---- subgroup_kernels.hip ("Subgroup membership")
+// ok[j] = 1 if pts[j] (affine Montgomery, on the curve, (0, 0) = infinity) is infinity or lies in the
+// prime-order subgroup, else 0. One point per lane; at most kSubgroupMaxBlocks blocks of kSubgroupLanes
+// lanes, which stride over the rest.
+static constexpr uint32_t kSubgroupLanes = 64, kSubgroupMaxBlocks = 4096;
+void launch_in_subgroup_g1(const G1Aff* pts, uint64_t n, uint8_t* ok, hipStream_t s);
+void launch_in_subgroup_g2(const G2Aff* pts, uint64_t n, uint8_t* ok, hipStream_t s);
+// out2[0] += the number of zeros in ok[0 .. n), out2[1] = min(out2[1], the first zero's index)
+void launch_ok_scan(const uint8_t* ok, uint64_t n, uint64_t* out2, hipStream_t s);
+
 }  // namespace spx

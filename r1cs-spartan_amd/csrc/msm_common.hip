@@ -858,8 +858,8 @@ __global__ void k_points_from_bytes(Fq* pts, uint64_t n, int* err) {
             continue;
         }
         // on the curve: y^2 = x^3 + b, b = 4 (G1) or 4 (1 + u) (G2); ark's CanonicalDeserialize of the
-        // PublicParameter rejects such points too (the subgroup check is not repeated: the PP is trusted
-        // input from setup, as in the reference's cache, commitment/mod.rs:41-62)
+        // PublicParameter rejects such points too. Its subgroup check is not made here (load time a
+        // trusted file does not need): spx_pp_check_subgroup makes it on request (subgroup_kernels.hip)
         if constexpr (NF == 2) {
             Fq y2, x3, b;
             fe_sqr(y2, m[1]);

@@ -110,6 +110,15 @@ void Ctx::set_msm_hot(int mode) {
     msm_ws_set_hot(msm, on);
     msm_ws_set_hot(msm_side, on);
 }
+// SPX_SUBGROUP_CHECK=1: contexts check proof points for subgroup membership unless told otherwise
+static bool subgroup_check_default() {
+    static const bool v = [] {
+        const char* e = getenv("SPX_SUBGROUP_CHECK");
+        return e && e[0] == '1' && e[1] == 0;
+    }();
+    return v;
+}
+bool Ctx::subgroup_check() const { return subgroup_mode < 0 ? subgroup_check_default() : subgroup_mode == 1; }
 Ctx::~Ctx() {
     (void)hipSetDevice(device);
     if (msm_side) msm_ws_destroy(msm_side);
@@ -2168,6 +2177,19 @@ struct ProofReader {
     // lazy: points stay bytes (spx_verify_many decompresses a whole batch's points on the GPU); the
     // callers keep each point's offset
     bool lazy = false;
+    // strict: the context whose subgroup check is on ("Subgroup membership"). Every point is
+    // tested right after it decompresses, as arkworks' checked deserialization does; `field` names the
+    // point being read for the error
+    Ctx* strict = nullptr;
+    std::string field;
+    template <class A, class Fn>
+    void member(const A& a, Fn&& in_subgroup) {
+        if (!strict || lazy) return;
+        strict->sgstat[1] += 1;
+        if (in_subgroup(a)) return;
+        strict->sgstat[2] += 1;
+        throw SpxError(kSerialization, field + " is not in the prime-order subgroup");
+    }
     const uint8_t* take(size_t k) {
         if (pos + k > len) throw SpxError(kSerialization, "truncated proof");
         const uint8_t* p = b + pos;
@@ -2188,12 +2210,14 @@ struct ProofReader {
         host::Affine<HFq> a{HFq::zero(), HFq::zero(), false};
         const uint8_t* p = take(48);
         if (!lazy && !host::g1_decompress(a, p)) throw SpxError(kSerialization, "invalid G1 point");
+        member(a, host::g1_in_subgroup);
         return a;
     }
     host::Affine<HFq2> g2() {
         host::Affine<HFq2> a{HFq2::zero(), HFq2::zero(), false};
         const uint8_t* p = take(96);
         if (!lazy && !host::g2_decompress(a, p)) throw SpxError(kSerialization, "invalid G2 point");
+        member(a, host::g2_in_subgroup);
         return a;
     }
 };
@@ -2204,15 +2228,17 @@ struct OpenProof {
     size_t h_at = 0;             // byte offsets of the compressed points in the proof
     std::vector<size_t> at;
 };
-OpenProof read_open(ProofReader& R) {
+OpenProof read_open(ProofReader& R, const char* name) {
     OpenProof o;
     o.eval = R.fr();
     o.h_at = R.pos;
+    if (R.strict) R.field = std::string(name) + " h";
     o.h = R.g2();
     const uint64_t k = R.u64();
     if (k > 64) throw SpxError(kSerialization, "bad opening proof length");
     for (uint64_t i = 0; i < k; ++i) {
         o.at.push_back(R.pos);
+        if (R.strict) R.field = std::string(name) + " proof point " + std::to_string(i);
         o.proofs.push_back(R.g2());
     }
     return o;
@@ -2357,16 +2383,19 @@ struct ParsedProof {
     std::vector<std::pair<size_t, size_t>> sp1, sp2;
     HFr va, vb, vc;
 };
-ParsedProof parse_proof(const uint8_t* proof, size_t len, bool lazy) {
+// strict: the context when its subgroup check is on, else null (ProofReader::strict)
+ParsedProof parse_proof(const uint8_t* proof, size_t len, bool lazy, Ctx* strict = nullptr) {
     ParsedProof P;
     ProofReader R{proof, len};
     R.lazy = lazy;
+    R.strict = strict;
+    R.field = "commitment";
     P.pm1_at = R.pos;
     (void)R.u64();  // the commitment's nv
     P.com_at = R.pos;
     P.com = R.g1();
     P.pm1_len = R.pos - P.pm1_at, P.pm2_at = R.pos;
-    P.op1 = read_open(R);
+    P.op1 = read_open(R, "opening 1");
     P.pm2_len = R.pos - P.pm2_at, P.pm3_at = R.pos;
     P.mm1 = R.u64(), P.nv1 = R.u64();
     P.sc1 = read_msgs(R, P.sp1);
@@ -2376,7 +2405,7 @@ ParsedProof parse_proof(const uint8_t* proof, size_t len, bool lazy) {
     P.mm2 = R.u64(), P.nv2 = R.u64();
     P.sc2 = read_msgs(R, P.sp2);
     P.pm6_at = R.pos;
-    P.op2 = read_open(R);
+    P.op2 = read_open(R, "opening 2");
     P.pm6_len = R.pos - P.pm6_at;
     if (R.pos != len) throw SpxError(kSerialization, "trailing bytes in proof");
     return P;
@@ -2454,7 +2483,7 @@ void verify(Ctx& C, Index& I, const uint8_t* v, size_t nv, const uint8_t* proof,
     if (I.G != 1) invalid("verify needs an index built on a single-rank context");
     const int L = I.log_n;
     const std::vector<HFr> vv = parse_public(v, nv, I.n);
-    const ParsedProof P = parse_proof(proof, len, false);
+    const ParsedProof P = parse_proof(proof, len, false, C.subgroup_check() ? &C : nullptr);
     const Challenges c = replay_transcript(P, proof, v, nv, L, matrices_state(I, o), o);
     // verify_sixth_round (verifier.rs:443-512)
     if (V.nv != L) invalid("verifier parameter nv != log_n");
@@ -2545,6 +2574,7 @@ void verify_many(Ctx& C, Index& I, const uint8_t* const* v, const size_t* nv, co
                  const uint8_t* entropy32, std::vector<int>& status, std::vector<std::string>& msgs) {
     if (I.G != 1) invalid("verify needs an index built on a single-rank context");
     const int L = I.log_n;
+    const bool strict = C.subgroup_check();  // the single-proof path reads the same setting
     status.assign(k, kOk);
     msgs.assign(k, std::string());
     struct Item {
@@ -2592,7 +2622,9 @@ void verify_many(Ctx& C, Index& I, const uint8_t* const* v, const size_t* nv, co
         // (d) first half: all points of the batch to the GPU, one launch per curve. G2 order: level i of
         // opening o at i m + o (the A_i are segments, B is the whole run), then the openings' h points.
         Mirror M{nullptr, nullptr};
-        const size_t cin1 = M.take(48 * n1), cin2 = M.take(96 * n2), okb = M.take(n1 + n2);
+        // strict: a second run of n1 + n2 flags behind the decompression's, the membership kernels'
+        const size_t nok = strict ? 2 * (n1 + n2) : n1 + n2;
+        const size_t cin1 = M.take(48 * n1), cin2 = M.take(96 * n2), okb = M.take(nok);
         const size_t sc1 = M.take(32 * (n1 + 1)), scA = M.take(32 * nq), scB = M.take(32 * nq);
         const size_t seg = M.take(8 * (L + 1 + 4)), gpt = M.take(96);
         const size_t outs = M.take(192 * (L + 1) + 96);
@@ -2617,7 +2649,12 @@ void verify_many(Ctx& C, Index& I, const uint8_t* const* v, const size_t* nv, co
         SPX_HIP(hipMemcpyAsync(M.d + cin1, M.h + cin1, cin2 + 96 * n2 - cin1, hipMemcpyHostToDevice, C.stream));
         launch_decompress_g1(M.d + cin1, n1, reinterpret_cast<G1Aff*>(M.d + pts1), M.d + okb, C.stream);
         launch_decompress_g2(M.d + cin2, n2, reinterpret_cast<G2Aff*>(M.d + pts2), M.d + okb + n1, C.stream);
-        SPX_HIP(hipMemcpyAsync(M.h + okb, M.d + okb, n1 + n2, hipMemcpyDeviceToHost, C.stream));
+        if (strict) {  // on the points where they lie, behind their decompression on the same stream
+            launch_in_subgroup_g1(reinterpret_cast<const G1Aff*>(M.d + pts1), n1, M.d + okb + n1 + n2, C.stream);
+            launch_in_subgroup_g2(reinterpret_cast<const G2Aff*>(M.d + pts2), n2, M.d + okb + n1 + n2 + n1, C.stream);
+            C.sgstat[0] += n1 + n2;
+        }
+        SPX_HIP(hipMemcpyAsync(M.h + okb, M.d + okb, nok, hipMemcpyDeviceToHost, C.stream));
         C.vstat[3] += n1 + n2;
         // (b) the algebraic checks, on the host while the points decompress
         for (int j : batch) {
@@ -2634,6 +2671,14 @@ void verify_many(Ctx& C, Index& I, const uint8_t* const* v, const size_t* nv, co
             for (int op = 0; op < 2; ++op) {
                 const size_t oi = 2 * b + op;
                 for (int i = 0; i <= L; ++i) ok &= M.h[okb + n1 + (size_t)i * m + oi] != 0;
+            }
+            // a point outside the subgroup leaves the batch as one that failed decompression does (the
+            // flags of the membership kernels have the decompression's layout)
+            if (strict) {
+                const size_t q = n1 + n2;
+                ok &= M.h[okb + q + b] != 0;
+                for (int op = 0; op < 2; ++op)
+                    for (int i = 0; i <= L; ++i) ok &= M.h[okb + q + n1 + (size_t)i * m + 2 * b + op] != 0;
             }
             if (!ok) it[batch[b]].live = false;
         }
@@ -2806,6 +2851,87 @@ void k_lincomb(Ctx& C, bool g2, const uint8_t* bases, const uint8_t* scalars, si
             p[ps - 1] |= host::kFlagInf;
         }
     }
+}
+
+// ---- subgroup membership: the kernel-level entry and the public-parameter check
+void k_in_subgroup(Ctx& C, bool g2, const uint8_t* pts, size_t n, uint8_t* ok) {
+    if (n == 0) invalid("no points");
+    // the encoding and the curve equation on the host, point by point (the kernel takes points on the
+    // curve); a point that fails either goes up as the infinity sentinel and is reported 0
+    const size_t ps = g2 ? 192 : 96;
+    std::vector<uint8_t> mont(ps * n, 0), valid(n, 1);
+    for (size_t j = 0; j < n; ++j) {
+        uint8_t* d = mont.data() + ps * j;
+        if (g2) {
+            host::Affine<HFq2> a;
+            valid[j] = host::g2_from_uncompressed(a, pts + ps * j) && host::on_curve(a);
+            if (valid[j] && !a.inf) memcpy(d, &a.x, 96), memcpy(d + 96, &a.y, 96);
+        } else {
+            host::Affine<HFq> a;
+            valid[j] = host::g1_from_uncompressed(a, pts + ps * j) && host::on_curve(a);
+            if (valid[j] && !a.inf) memcpy(d, &a.x, 48), memcpy(d + 48, &a.y, 48);
+        }
+    }
+    DevMem dp(ps * n), dok(n);
+    SPX_HIP(hipMemcpyAsync(dp.p, mont.data(), ps * n, hipMemcpyHostToDevice, C.stream));
+    if (g2)
+        launch_in_subgroup_g2(dp.as<G2Aff>(), n, dok.as<uint8_t>(), C.stream);
+    else
+        launch_in_subgroup_g1(dp.as<G1Aff>(), n, dok.as<uint8_t>(), C.stream);
+    SPX_HIP(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    uint64_t rejected = 0;
+    for (size_t j = 0; j < n; ++j) {
+        ok[j] = ok[j] && valid[j] ? 1 : 0;
+        rejected += !ok[j];
+    }
+    C.sgstat[0] += n;
+    C.sgstat[2] += rejected;
+}
+
+PPSubgroupReport pp_check_subgroup(Ctx& C, const PP& P) {
+    const int nv = P.nv;
+    const uint64_t tot = P.lvl_off[nv];
+    // every raw level of a curve in one launch (the levels are contiguous), then the count of the
+    // rejected points and the lowest one's index
+    DevMem ok(2 * tot), res(32);
+    const uint64_t init[4] = {0, ~0ull, 0, ~0ull};
+    uint64_t got[4];
+    SPX_HIP(hipMemcpyAsync(res.p, init, 32, hipMemcpyHostToDevice, C.stream));
+    launch_in_subgroup_g1(P.g1_raw_mem.as<G1Aff>(), tot, ok.as<uint8_t>(), C.stream);
+    launch_in_subgroup_g2(P.g2_raw_mem.as<G2Aff>(), tot, ok.as<uint8_t>() + tot, C.stream);
+    launch_ok_scan(ok.as<uint8_t>(), tot, res.as<uint64_t>(), C.stream);
+    launch_ok_scan(ok.as<uint8_t>() + tot, tot, res.as<uint64_t>() + 2, C.stream);
+    SPX_HIP(hipMemcpyAsync(got, res.p, 32, hipMemcpyDeviceToHost, C.stream));
+    // g and h on the host meanwhile
+    const bool g_ok = host::on_curve(P.g) && host::g1_in_subgroup(P.g);
+    const bool h_ok = host::on_curve(P.h) && host::g2_in_subgroup(P.h);
+    C.sync();
+    PPSubgroupReport r;
+    r.bad = got[0] + got[2] + !g_ok + !h_ok;
+    C.sgstat[0] += 2 * tot;
+    C.sgstat[1] += 2;
+    C.sgstat[2] += r.bad;
+    if (!r.bad) return r;
+    // the lowest offender in the order G1 levels, G2 levels, g, h
+    auto level_of = [&](uint64_t idx) {
+        int i = 0;
+        while (idx >= P.lvl_off[i + 1]) ++i;
+        return i;
+    };
+    if (got[0] || got[2]) {
+        const int c = got[0] ? 0 : 1;
+        const uint64_t idx = got[2 * c + 1];
+        const int lvl = level_of(idx);
+        r.first[0] = (uint64_t)c + 1, r.first[1] = (uint64_t)lvl, r.first[2] = idx - P.lvl_off[lvl];
+        r.message = std::string(c ? "powers_of_h" : "powers_of_g") + " level " + std::to_string(lvl) + " index " + std::to_string(r.first[2]);
+    } else {
+        r.first[0] = g_ok ? 2 : 1, r.first[1] = ~0ull, r.first[2] = 0;
+        r.message = g_ok ? "h" : "g";
+    }
+    r.message = "public parameter point outside the prime-order subgroup: " + r.message + " (" +
+                std::to_string(r.bad) + " such point" + (r.bad == 1 ? "" : "s") + ")";
+    return r;
 }
 
 static HostCsr single(const HostCsr& m) { return m; }

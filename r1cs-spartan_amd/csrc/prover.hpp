@@ -248,6 +248,12 @@ struct Ctx {
     DevMem vdev;
     PinBuf vpin;
     std::atomic<uint64_t> vstat[4] = {};
+    // subgroup membership of proof points in verify / verify_many: 1 on, 0 off, -1 the
+    // process default (SPX_SUBGROUP_CHECK=1 -> on, else off); and the counters of every membership
+    // check made through this context: points checked on the GPU, on the host, points rejected
+    int subgroup_mode = -1;
+    bool subgroup_check() const;
+    std::atomic<uint64_t> sgstat[3] = {};
     Ctx(int dev);
     ~Ctx();
     // region [off, off + bytes) of the pinned carve-out (throws if it does not fit its region)
@@ -456,6 +462,18 @@ void k_decompress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out, ui
 // out[s] = sum over segment s of scalar_i base_i; uncompressed ark bytes in and out
 void k_lincomb(Ctx& C, bool g2, const uint8_t* bases, const uint8_t* scalars, size_t n, const uint64_t* seg_off,
                size_t nseg, uint8_t* out);
+
+// subgroup membership: ok[j] = 1 if uncompressed point j is canonical, on the curve and in
+// the prime-order subgroup (infinity included); the membership test runs on the GPU
+void k_in_subgroup(Ctx& C, bool g2, const uint8_t* pts, size_t n, uint8_t* ok);
+// every raw G1 and G2 level of a public parameter on the GPU, g and h on the host. first = {curve (1 |
+// 2), level or ~0 for g / h, index} of the lowest offender in the order G1 levels, G2 levels, g, h
+struct PPSubgroupReport {
+    uint64_t bad = 0;
+    uint64_t first[3] = {0, 0, 0};
+    std::string message;  // names the first offender; empty when bad = 0
+};
+PPSubgroupReport pp_check_subgroup(Ctx& C, const PP& P);
 
 std::vector<uint8_t> k_sum_over_y(Ctx& C, const HostCsr& m, const uint8_t* z);
 std::vector<uint8_t> k_eval_on_x(Ctx& C, const HostCsr& m, const uint8_t* r_x);
