@@ -230,10 +230,13 @@ DEV void fe_inv(Fe<C>& r, const Fe<C>& a) {
     constexpr int N = C::N;
     Fe<C> acc;
     fe_one(acc);
-    // exponent p - 2 (p odd, low limb >= 3 for both moduli)
+    // exponent p - 2. q's low limb is >= 2; r's is 1, so r - 2 borrows 1 from limb 1 (0xffffffff: no
+    // further borrow)
+    constexpr bool kBorrow = (N == 8 ? kFrP[0] : kFqP[0]) < 2u;
+    static_assert(!kBorrow || (N == 8 ? kFrP[1] : kFqP[1]) != 0u, "borrow stops at limb 1");
 #pragma unroll 1
     for (int i = N - 1; i >= 0; --i) {
-        uint32_t e = PCfg<C>::p(i) - (i == 0 ? 2u : 0u);
+        uint32_t e = PCfg<C>::p(i) - (i == 0 ? 2u : (kBorrow && i == 1) ? 1u : 0u);
 #pragma unroll 1
         for (int b = 31; b >= 0; --b) {
             fe_sqr(acc, acc);
