@@ -419,6 +419,30 @@ int spx_ctx_set_subgroup_check(spx_ctx *ctx, int mode);
  * checked on the host, out[2] points rejected as reported to the caller (ok = 0, a public parameter's
  * offenders, a strict spx_verify's error; a batch's rejected point counts once, on the single-proof path) */
 int spx_subgroup_stats(spx_ctx *ctx, uint64_t out[3]);
+/* ---- witness check: reject a witness with (Az)o(Bz) != Cz on the GPU before proving it.
+ * The check is of the tables the proof is built from: Az, Bz, Cz as the prover's sum_over_y computes them
+ * (r1cs_reader.rs:75-85). For a matrix row that names a column more than once the last entry wins, as in
+ * the proof, not ark-relations' sum of the entries.
+ * 0 = off (the default: every call behaves as before), 1 = on, -1 = process default (SPX_WITNESS_CHECK=1 -> on).
+ * SPX_INVALID_ARGUMENT while the context is in use. Every rank of a proof-sharded prove must use the same
+ * mode (ranks that differ fail their next sharded prove with SPX_INVALID_ARGUMENT).
+ * On: spx_prove, spx_prove_witness and spx_prover_first_round return SPX_WRONG_WITNESS for a witness that
+ * violates a constraint, with "constraint 37 is not satisfied: (Az)(Bz) != Cz (5 of 256 constraints fail)"
+ * in spx_last_error (the lowest violated row); no proof byte is written and *len is left untouched. The
+ * check is one kernel behind the prover's first one and is read at the proof's first host wait.
+ * spx_prove_many sets lens[i] = 0 for a rejected witness, goes on to that worker's next proof, produces
+ * every other proof and returns SPX_WRONG_WITNESS, spx_last_error naming the lowest rejected proof index
+ * and its row ("proof 2: constraint ..."); any other failure stops its worker and is returned as before.
+ * spx_witness_check on a rejected witness gives its row. */
+int spx_ctx_set_witness_check(spx_ctx *ctx, int mode);
+/* SPX_OK with *bad = 0, or SPX_WRONG_WITNESS with *bad = number of violated constraints, *first_row = the
+ * lowest one, abc = Az, Bz, Cz of that row as canonical Fr (96 B). bad, first_row, abc may each be NULL.
+ * (*first_row = UINT64_MAX and abc = 0 when nothing is violated.) Runs whatever the context's mode is; on
+ * a proof-sharded context every rank must call it, and every rank gets the same answer. */
+int spx_witness_check(spx_ctx *ctx, spx_pk *idx, spx_witness *wit, uint64_t *bad, uint64_t *first_row, uint8_t *abc);
+/* cumulative, this context: out[0] witnesses checked, out[1] witnesses rejected, out[2] check kernel
+ * launches (a lockstep group's checks are one), out[3] rows checked. All stay put while the check is off. */
+int spx_witness_check_stats(spx_ctx *ctx, uint64_t out[4]);
 int spx_commit(spx_ctx *ctx, spx_pp *pp, const uint8_t *table, int nv, uint8_t *out56);
 /* proof_out: Proof{h, proofs} compressed = 96 + 8 + 96 * nv bytes */
 int spx_open(spx_ctx *ctx, spx_pp *pp, const uint8_t *table, int nv, const uint8_t *point, uint8_t *eval_out,

@@ -157,6 +157,9 @@ EXPORTED = [
     "spx_pp_check_subgroup",
     "spx_ctx_set_subgroup_check",
     "spx_subgroup_stats",
+    "spx_ctx_set_witness_check",
+    "spx_witness_check",
+    "spx_witness_check_stats",
     "spx_commit",
     "spx_open",
 ]
@@ -252,6 +255,11 @@ def lib():
         L.spx_pp_check_subgroup.argtypes = [vp, vp, pu64, pu64]
         L.spx_ctx_set_subgroup_check.argtypes = [vp, ctypes.c_int]
         L.spx_subgroup_stats.argtypes = [vp, pu64]
+    if hasattr(L, "spx_witness_check") or not os.environ.get("SPX_LIB_PATH"):  # A/B builds may predate it
+        pu64 = ctypes.POINTER(ctypes.c_uint64)
+        L.spx_ctx_set_witness_check.argtypes = [vp, ctypes.c_int]
+        L.spx_witness_check.argtypes = [vp, vp, vp, pu64, pu64, ctypes.c_void_p]
+        L.spx_witness_check_stats.argtypes = [vp, pu64]
     if hasattr(L, "spx_hash_stats") or not os.environ.get("SPX_LIB_PATH"):
         L.spx_hash_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.spx_vp_from_pp.argtypes = [vp, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
@@ -405,6 +413,20 @@ class Context:
         checks made through this context, cumulative (spx_subgroup_stats)"""
         v = (ctypes.c_uint64 * 3)()
         _check(lib().spx_subgroup_stats(self.h, v))
+        return tuple(int(x) for x in v)
+
+    def set_witness_check(self, mode):
+        """witness check of every prove on this context: 1 on, 0 off (the default), -1 the process
+        default (SPX_WITNESS_CHECK=1 -> on). On: a witness with (Az)(Bz) != Cz in some row raises
+        WrongWitness naming the lowest such row instead of yielding a worthless proof; every rank of a
+        proof-sharded prove must use the same mode (spx_ctx_set_witness_check)"""
+        _check(lib().spx_ctx_set_witness_check(self.h, int(mode)))
+
+    def witness_check_stats(self):
+        """(witnesses checked, witnesses rejected, check kernel launches, rows checked) on this context,
+        cumulative (spx_witness_check_stats)"""
+        v = (ctypes.c_uint64 * 4)()
+        _check(lib().spx_witness_check_stats(self.h, v))
         return tuple(int(x) for x in v)
 
     def msm_skew_stats(self):
@@ -756,7 +778,9 @@ class MLArgumentForR1CS:
 
     @staticmethod
     def prove_many(ctxs, pk, wits, pp, mode="fs", seed=0, cached=False, commitment_stub=False):
-        """Proves every witness in `wits` concurrently, one worker per context (spx_prove_many)."""
+        """Proves every witness in `wits` concurrently, one worker per context (spx_prove_many). With
+        the contexts' witness check on, rejected witnesses raise WrongWitness after every other proof
+        is produced: its `.proofs` is the list of proofs with None at the rejected ones."""
         cap = lib().spx_proof_size(pk.log_n, 0)
         n = len(wits)
         out = ctypes.create_string_buffer(cap * max(n, 1))
@@ -764,10 +788,27 @@ class MLArgumentForR1CS:
         ch = (ctypes.c_void_p * len(ctxs))(*[c.h for c in ctxs])
         wh = (ctypes.c_void_p * max(n, 1))(*[w.h for w in wits])
         o = _opts(mode, seed, cached, commitment_stub)
-        _check(lib().spx_prove_many(ch, len(ctxs), pk.h, wh, n, _pp_handle(pp, commitment_stub), ctypes.byref(o), out,
-                                    cap, lens))
+        rc = lib().spx_prove_many(ch, len(ctxs), pk.h, wh, n, _pp_handle(pp, commitment_stub), ctypes.byref(o), out,
+                                  cap, lens)
         raw = out.raw
+        if rc == 3:  # SPX_WRONG_WITNESS: the witness check rejected some; the others are proved
+            e = WrongWitness(lib().spx_last_error().decode(errors="replace"))
+            e.proofs = [raw[i * cap : i * cap + lens[i]] if lens[i] else None for i in range(n)]
+            raise e
+        _check(rc)
         return [raw[i * cap : i * cap + lens[i]] for i in range(n)]
+
+    @staticmethod
+    def check_witness(pk, wit):
+        """(bad, first_row, (az, bz, cz)): the number of constraints with (Az)(Bz) != Cz, the lowest
+        such row (None if none) and Az, Bz, Cz there as ints, from the GPU (spx_witness_check). Does not
+        raise for a violated constraint. On a proof-sharded context every rank must call it."""
+        bad, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        abc = ctypes.create_string_buffer(96)
+        rc = lib().spx_witness_check(pk.ctx.h, pk.h, wit.h, ctypes.byref(bad), ctypes.byref(first), abc)
+        if rc != 3:
+            _check(rc)
+        return int(bad.value), (int(first.value) if bad.value else None), tuple(fr_ints(abc.raw))
 
 
     @staticmethod

@@ -536,6 +536,13 @@ int spx_prove_many(spx_ctx** ctxs, int nctx, spx_pk* idx, spx_witness** wits, in
 
     std::vector<int> st(nctx, SPX_OK);
     std::vector<std::string> msg(nctx);
+    // witnesses the contexts' witness check rejected (spx_ctx_set_witness_check): lens[i] = 0 and the
+    // worker goes on; each slot is written by its proof's worker only
+    std::vector<std::string> rejected(nproofs);
+    auto reject = [&](int i, const std::string& why) {
+        lens[i] = 0;
+        rejected[i] = why;
+    };
     auto opts_for = [&](int i) {
         spx::ProveOpts o = base;
         o.seq = i;
@@ -577,9 +584,20 @@ int spx_prove_many(spx_ctx** ctxs, int nctx, spx_pk* idx, spx_witness** wits, in
                     os.push_back(opts_for(mine[a + q]));
                     ws.push_back(wits[mine[a + q]]->w.get());
                 }
-                auto ps = spx::prove_group(*ctxs[k]->c, *idx->i, ws.data(), cnt, os.data());
-                for (int q = 0; q < cnt; ++q) emit(mine[a + q], ps[q]);
+                std::vector<std::string> why;
+                auto ps = spx::prove_group(*ctxs[k]->c, *idx->i, ws.data(), cnt, os.data(), &why);
+                for (int q = 0; q < cnt; ++q) {
+                    if (why[q].empty())
+                        emit(mine[a + q], ps[q]);
+                    else
+                        reject(mine[a + q], why[q]);
+                }
             });
+            // the prover throws SPX_WRONG_WITNESS only from the witness check: that proof alone is dropped
+            if (rc == SPX_WRONG_WITNESS && !grouped && ctxs[k]->c->witness_check()) {
+                reject(mine[a], g_err);
+                continue;
+            }
             if (rc != SPX_OK) {
                 st[k] = rc;
                 msg[k] = g_err;
@@ -598,6 +616,11 @@ int spx_prove_many(spx_ctx** ctxs, int nctx, spx_pk* idx, spx_witness** wits, in
         if (st[k] != SPX_OK) {
             g_err = msg[k];
             return st[k];
+        }
+    for (int i = 0; i < nproofs; ++i)
+        if (!rejected[i].empty()) {
+            g_err = "proof " + std::to_string(i) + ": " + rejected[i];
+            return SPX_WRONG_WITNESS;
         }
     g_err.clear();
     return SPX_OK;
@@ -903,6 +926,34 @@ int spx_subgroup_stats(spx_ctx* ctx, uint64_t out[3]) {
     return guard([&] {
         if (!ctx || !out) spx::invalid("null argument");
         for (int i = 0; i < 3; ++i) out[i] = ctx->c->sgstat[i].load();
+    });
+}
+
+// ---- witness check
+int spx_ctx_set_witness_check(spx_ctx* ctx, int mode) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (mode < -1 || mode > 1) spx::invalid("witness check mode must be -1, 0 or 1");
+        if (ctx->c->in_use.load()) spx::invalid("context in use by a prove or session");
+        ctx->c->witness_check_mode = mode;
+        ctx->c->knobs_agreed = false;
+    });
+}
+int spx_witness_check(spx_ctx* ctx, spx_pk* idx, spx_witness* wit, uint64_t* bad, uint64_t* first_row, uint8_t* abc) {
+    return guard([&] {
+        set_dev(ctx);
+        if (!idx || !wit) spx::invalid("null prover key / witness");
+        const spx::WitnessReport r = spx::check_witness(*ctx->c, *idx->i, *wit->w);
+        if (bad) *bad = r.bad;
+        if (first_row) *first_row = r.first_row;
+        if (abc) memcpy(abc, r.abc, 96);
+        if (r.bad) throw spx::SpxError(spx::kWrongWitness, r.message());
+    });
+}
+int spx_witness_check_stats(spx_ctx* ctx, uint64_t out[4]) {
+    return guard([&] {
+        if (!ctx || !out) spx::invalid("null argument");
+        for (int i = 0; i < 4; ++i) out[i] = ctx->c->wcstat[i].load();
     });
 }
 

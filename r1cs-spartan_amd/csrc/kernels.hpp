@@ -240,6 +240,24 @@ void launch_open_eval_group(int k, const Fr* const* z, Fr* const* bufA, Fr* cons
 // one launch
 void launch_copy_runs_group(int k, const Tables3* src, int nruns, int per, Fr* const* dst, hipStream_t s);
 void launch_open_level(const Fr* rin, Fr* rout, Fr* q, const Fr& point, uint64_t half, hipStream_t s);
+// Witness check (k_r1cs_check): over the rank-local tables Az, Bz, Cz (nl rows each, row0 =
+// the global index of local row 0) the rows with Az[i] Bz[i] != Cz[i] are counted and the lowest one is
+// found. One job per proof (blockIdx.y; k <= kGroupMax), one launch, no other launch or copy:
+//   partial: 2 x uint64 per block of the launch (at most kR1csMaxBlocks blocks);
+//   ticket:  a device counter that is 0 (left 0), as the sumcheck rounds';
+//   record:  kR1csRecordWords uint64 (device or host-mapped pinned memory, 16-byte aligned): the count,
+//            the global first row (UINT64_MAX if none), then Az, Bz, Cz of that row (Montgomery; zero if
+//            none). A count and a minimum: independent of the order the blocks ran in.
+static constexpr int kR1csMaxBlocks = 2048;
+static constexpr int kR1csRecordWords = 14;
+static constexpr size_t kR1csRecordStride = 128;  // bytes between the records of a group
+struct R1csCheckJob {
+    const Fr *az, *bz, *cz;
+    uint64_t* partial;
+    uint32_t* ticket;
+    uint64_t* record;
+};
+void launch_r1cs_check(int k, const R1csCheckJob* jobs, uint64_t nl, uint64_t row0, hipStream_t s);
 // the last levels of an opening in one launch: how many of the `remaining` levels starting at a level
 // of `half` pairs it takes (0: none), and the launch (points[j] folds level j; q receives the levels'
 // quotients contiguously; `last` the final value)

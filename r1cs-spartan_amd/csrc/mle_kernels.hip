@@ -1322,6 +1322,108 @@ __global__ void k_copy_runs_group(GroupOf<CopyJob> g, int n, int per) {
     for (int t = threadIdx.x; t < n * per; t += blockDim.x) st_fr(j.dst + t, ld_fr(j.src[t / per] + t % per));
 }
 
+// ------------------------------------------------------------------ witness check
+// Rows of the local tables with Az Bz != Cz: their number and the lowest one. One row per lane and
+// iteration, adjacent lanes on adjacent 32-byte elements (the kernel is a 96-byte-per-row stream with one
+// Fr product per row: one product chain per lane keeps it at 67 VGPRs, 7 waves per SIMD, which is what
+// hides the loads; fr_mul_pair's second chain is for kernels that run fewer). The loop is uniform over
+// the block, so the round's violations are a ballot; the lowest row of a lane is its first.
+DEV uint64_t wave_min_u64(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint64_t o = __shfl_xor((unsigned long long)v, m, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+DEV uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor((unsigned long long)v, m, 64);
+    return v;
+}
+// the block's count and minimum from its waves' (valid in thread 0); lds: 2 x kThreads / 64 words, free
+// for reuse after the next barrier
+DEV void r1cs_block_combine(uint64_t& cnt, uint64_t& first, uint64_t* lds) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) {
+        lds[wid] = cnt;
+        lds[kThreads / 64 + wid] = first;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt = 0;
+        first = ~0ull;
+        for (int w = 0; w < kThreads / 64; ++w) {
+            cnt += lds[w];
+            first = lds[kThreads / 64 + w] < first ? lds[kThreads / 64 + w] : first;
+        }
+    }
+}
+DEV void r1cs_write_record(const R1csCheckJob& j, uint64_t cnt, uint64_t first, uint64_t row0) {
+    Fr a, b, c;
+    fe_zero(a), fe_zero(b), fe_zero(c);
+    uint64_t g = ~0ull;
+    if (first != ~0ull) {
+        g = row0 + first;
+        a = ld_fr(j.az + first), b = ld_fr(j.bz + first), c = ld_fr(j.cz + first);
+    }
+    uint4* rec = reinterpret_cast<uint4*>(j.record);
+    rec[0] = make_uint4((uint32_t)cnt, (uint32_t)(cnt >> 32), (uint32_t)g, (uint32_t)(g >> 32));
+    Fr* abc = reinterpret_cast<Fr*>(rec + 1);
+    st_fr(abc, a), st_fr(abc + 1, b), st_fr(abc + 2, c);
+}
+__global__ __launch_bounds__(kThreads) void k_r1cs_check(GroupOf<R1csCheckJob> g, uint64_t nl, uint64_t row0) {
+    const R1csCheckJob& j = g.j[blockIdx.y];
+    __shared__ uint64_t lds[2 * (kThreads / 64)];
+    __shared__ bool last;
+    uint64_t cnt = 0, first = ~0ull;
+    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t b0 = (uint64_t)blockIdx.x * kThreads; b0 < nl; b0 += stride) {
+        const uint64_t i = b0 + threadIdx.x;
+        bool bad = false;
+        if (i < nl) {
+            const Fr a = ld_fr(j.az + i), b = ld_fr(j.bz + i), c = ld_fr(j.cz + i);
+            Fr p;
+            fe_mul(p, a, b);
+            bad = !fe_eq(p, c);
+        }
+        cnt += __popcll(__ballot(bad));  // the wave's violations of this round (the same in every lane)
+        if (bad && first == ~0ull) first = i;
+    }
+    first = wave_min_u64(first);
+    r1cs_block_combine(cnt, first, lds);
+    if (gridDim.x == 1) {  // one block: its result is the record (no hand-off)
+        if (threadIdx.x == 0) r1cs_write_record(j, cnt, first, row0);
+        return;
+    }
+    // hand-off to the last block, as grid_reduce_last: agent-scope stores of the block's partial, drained,
+    // then the ticket; the block that drew the last one reads every partial with agent-scope loads
+    if (threadIdx.x == 0) {
+        gu64* dst = (gu64*)(j.partial + 2 * (size_t)blockIdx.x);
+        __hip_atomic_store(dst, (unsigned long long)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(dst + 1, (unsigned long long)first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partial has left this CU before the ticket
+        last = __hip_atomic_fetch_add((gu32*)j.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    cnt = 0, first = ~0ull;
+    for (uint32_t b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
+        const gu64* src = (const gu64*)(j.partial + 2 * (size_t)b);
+        cnt += __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t f = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        first = f < first ? f : first;
+    }
+    cnt = wave_sum_u64(cnt);
+    first = wave_min_u64(first);
+    r1cs_block_combine(cnt, first, lds);
+    if (threadIdx.x == 0) {
+        r1cs_write_record(j, cnt, first, row0);
+        *j.ticket = 0u;
+    }
+}
+static_assert(sizeof(GroupOf<R1csCheckJob>) <= 4096, "a group launch's arguments stay below 4 KiB");
+
 // ------------------------------------------------------------------ launchers
 static inline int grid_for(uint64_t n, int cap = 2048) {
     uint64_t g = (n + kThreads - 1) / kThreads;
@@ -1764,6 +1866,17 @@ void launch_open_level(const Fr* rin, Fr* rout, Fr* q, const Fr& point, uint64_t
     kp_begin(KP_OPEN, s);
     hipLaunchKernelGGL(k_open_level, dim3(grid_for(half, 8192)), dim3(kThreads), 0, s, rin, rout, q, point, half);
     kp_end(32.0 * (2.0 + (q ? 1.0 : 0.0) + (rout ? 1.0 : 0.0)) * (double)half, s);  // read 2, write q and/or r'
+}
+
+void launch_r1cs_check(int k, const R1csCheckJob* jobs, uint64_t nl, uint64_t row0, hipStream_t s) {
+    if (nl < 1) throw std::invalid_argument("witness check of an empty table");
+    GroupOf<R1csCheckJob> g = group_check<R1csCheckJob>(k);
+    for (int i = 0; i < k; ++i) g.j[i] = jobs[i];
+    // one row per lane for small tables; from 2^12 rows on four (a quarter of the partials and tickets),
+    // and past 2^21 rows whatever kR1csMaxBlocks blocks leave per lane
+    const uint64_t per = nl >= 4096 ? 4 : 1;
+    hipLaunchKernelGGL(k_r1cs_check, dim3(grid_for((nl + per - 1) / per, kR1csMaxBlocks), k), dim3(kThreads), 0, s, g, nl,
+                       row0);
 }
 
 }  // namespace spx

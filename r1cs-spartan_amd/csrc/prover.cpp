@@ -119,6 +119,15 @@ static bool subgroup_check_default() {
     return v;
 }
 bool Ctx::subgroup_check() const { return subgroup_mode < 0 ? subgroup_check_default() : subgroup_mode == 1; }
+// SPX_WITNESS_CHECK=1: contexts check every witness they prove unless told otherwise
+static bool witness_check_default() {
+    static const bool v = [] {
+        const char* e = getenv("SPX_WITNESS_CHECK");
+        return e && e[0] == '1' && e[1] == 0;
+    }();
+    return v;
+}
+bool Ctx::witness_check() const { return witness_check_mode < 0 ? witness_check_default() : witness_check_mode == 1; }
 Ctx::~Ctx() {
     (void)hipSetDevice(device);
     if (msm_side) msm_ws_destroy(msm_side);
@@ -984,11 +993,11 @@ static void commit_launch(Ctx& C, PP& P, const Fr* z, uint64_t n, const MsmShard
     const size_t ob = msm_out_bytes(false, 1);
     void* out = C.buf(Ctx::kSlotCommit, ob);
     msm_run_g1(C.msm, &inst, 1, P.g1_pre.as<G1Slot>(), z, out, C.stream, sh);
-    SPX_HIP(hipMemcpyAsync(C.pin_at(Ctx::kPinCommit, ob, 4 << 10), out, ob, hipMemcpyDeviceToHost, C.stream));
+    SPX_HIP(hipMemcpyAsync(C.pin_at(Ctx::kPinCommit, ob, 2 << 10), out, ob, hipMemcpyDeviceToHost, C.stream));
 }
 static Affine<HFq> commit_finish(Ctx& C, PP& P, const Fr* z, uint64_t n, Comm& comm) {
     C.sync();
-    const uint8_t* h = C.pin_at(Ctx::kPinCommit, msm_out_bytes(false, 1), 4 << 10);
+    const uint8_t* h = C.pin_at(Ctx::kPinCommit, msm_out_bytes(false, 1), 2 << 10);
     if (msm_status(h, false, 1) & kMsmOverflow) {  // compacted keys overflowed: once more with a slot per digit
         msm_ws_note_overflow(C.msm);
         ++C.msm_reruns;
@@ -1225,6 +1234,59 @@ static HFr quad_at(const HFr g[3], const HFr& t) {
 }
 
 // ====================================================================== prove
+// ---------------------------------------------------------------- witness check
+// The kernel writes each proof's record straight into the context's pinned carve-out (as the sumcheck
+// rounds write their sums): it is read after the next wait that covers the launch, no copy is queued.
+static_assert(kGroupMax * kR1csRecordStride <= (2 << 10) && 8 * kR1csRecordWords <= kR1csRecordStride,
+              "the group's records fit their pinned region");
+static uint8_t* witness_record(Ctx& C, int j) {
+    return C.pin_at(Ctx::kPinWitness, kGroupMax * kR1csRecordStride, 2 << 10) + kR1csRecordStride * j;
+}
+// proof j's job: its tables, 2 x kR1csMaxBlocks words of `partial`, the context's ticket j and record j
+static R1csCheckJob witness_job(Ctx& C, int j, const Fr* Az, const Fr* Bz, const Fr* Cz, Fr* partial) {
+    static_assert(16 * (uint64_t)kR1csMaxBlocks <= 32 * kRoundPartials, "the check's partials fit a proof's round partials");
+    return R1csCheckJob{Az, Bz, Cz, reinterpret_cast<uint64_t*>(partial), C.ticket + j,
+                        C.pin_dev<uint64_t>(witness_record(C, j))};
+}
+static void witness_check_launch(Ctx& C, const R1csCheckJob* jobs, int k, uint64_t nl, uint64_t row0) {
+    launch_r1cs_check(k, jobs, nl, row0, C.stream);
+    C.wcstat[2] += 1;
+    C.wcstat[3] += (uint64_t)k * nl;
+}
+std::string WitnessReport::message() const {
+    return "constraint " + std::to_string(first_row) + " is not satisfied: (Az)(Bz) != Cz (" + std::to_string(bad) +
+           " of " + std::to_string(rows) + " constraints fail)";
+}
+// Proof j's verdict, after a wait that covers its check. Sharded: one exchange of the ranks' records
+// (112 B each); every rank then holds the sum of the counts, the lowest first row and that row's values.
+static WitnessReport witness_verdict(Ctx& C, int j, Comm& comm, uint64_t n) {
+    constexpr size_t kRec = 8 * kR1csRecordWords;
+    const int G = comm.size();
+    std::vector<uint8_t> all(kRec * G);
+    if (G > 1)
+        comm.allgather(witness_record(C, j), all.data(), kRec);
+    else
+        memcpy(all.data(), witness_record(C, j), kRec);
+    WitnessReport rep;
+    rep.rows = n;
+    const uint8_t* at = nullptr;
+    for (int r = 0; r < G; ++r) {
+        uint64_t w[2];
+        memcpy(w, all.data() + kRec * r, 16);
+        rep.bad += w[0];
+        if (w[1] < rep.first_row) rep.first_row = w[1], at = all.data() + kRec * r + 16;
+    }
+    if (at)
+        for (int m = 0; m < 3; ++m) {
+            uint64_t c[4];
+            ld_hfr(at + 32 * m).to_canon(c);
+            memcpy(rep.abc + 32 * m, c, 32);
+        }
+    ++C.wcstat[0];
+    if (rep.bad) ++C.wcstat[1];
+    return rep;
+}
+
 std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts& o) {
     CtxClaim claim;
     if (!o.claimed) claim.take(C);  // before anything is queued: a refused prove touches nothing
@@ -1314,6 +1376,20 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
                            I.rows.lrows.as<LongRow>(), I.rows.nlrows, partial, C.stream);
         kp_end(I.rows_bytes, C.stream);
     }
+    // ---- witness check (off by default): one launch behind the SpMV; its record is read at the proof's
+    // first host wait (witness_checked below), so it adds no wait
+    const bool wcheck = C.witness_check();
+    if (wcheck) {
+        const R1csCheckJob job = witness_job(C, 0, Az, Bz, Cz, partial);
+        witness_check_launch(C, &job, 1, nl, lo);
+    }
+    auto witness_checked = [&] {
+        const WitnessReport rep = witness_verdict(C, 0, comm, n);
+        if (!rep.bad) return;
+        C.sync();  // what the proof has queued so far, both streams: the next prove starts clean
+        C.side_sync();
+        throw SpxError(kWrongWitness, rep.message());
+    };
     // The shared level-0 opening proof is launched right behind the commitment, before any challenge,
     // when the host has the matrix absorption to do meanwhile. With the index-cached transcript there
     // is nothing to hide it behind: a sharded proof then runs it on the context's second stream, beside
@@ -1340,11 +1416,14 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     if (G > 1 && !C.knobs_agreed) {
         // the level-0 mode decides the order and sizes of a proof's exchanges: every rank of the
         // communicator must read the same SPX_LVL0 (one exchange on a context's first sharded proof)
-        const uint32_t mine = lvl0_batch ? 1u : 0u;
+        // (and so does the witness check, which adds one: bit 1)
+        const uint32_t mine = (lvl0_batch ? 1u : 0u) | (wcheck ? 2u : 0u);
         std::vector<uint32_t> all(G);
         comm.allgather(&mine, all.data(), sizeof mine);
-        for (int r = 0; r < G; ++r)
-            if (all[r] != mine) invalid("SPX_LVL0 / level-0 mode differs between the ranks of this communicator");
+        for (int r = 0; r < G; ++r) {
+            if ((all[r] ^ mine) & 1u) invalid("SPX_LVL0 / level-0 mode differs between the ranks of this communicator");
+            if (all[r] != mine) invalid("SPX_WITNESS_CHECK / witness check mode differs between the ranks of this communicator");
+        }
         C.knobs_agreed = true;
     }
     const bool share0 = !o.stub;
@@ -1389,6 +1468,9 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     }
     mark("transcript_matrices", tp);
     Affine<HFq> com = o.stub ? Affine<HFq>{HFq::zero(), HFq::zero(), true} : commit_finish(C, *P, z, n, comm);
+    // the commitment's wait covered the check: before any challenge is drawn or message emitted (a
+    // stubbed proof has no wait here: its verdict follows its first opening's wait, below)
+    if (wcheck && !o.stub) witness_checked();
     Affine<HFq2> proof0{};
     if (early0) proof0 = lvl0_finish(C, *P, z, L, comm);
     Ser proof;
@@ -1407,6 +1489,7 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     {
         OpenOut op = o.stub ? open_stub(C, zl, L, pt1, G)
                             : open_z(C, *P, z, L, pt1, comm, (early0 || side0) ? &proof0 : nullptr);
+        if (wcheck && o.stub) witness_checked();  // the stubbed proof's first wait (r_v is derived, nothing emitted)
         if (side0) op.proofs[0] = proof0 = lvl0_finish(C, *P, z, L, comm, true);
         if (share0 && !early0 && !side0) proof0 = op.proofs[0];
         size_t m0 = proof.b.size();
@@ -1685,7 +1768,8 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
 // rounds are one launch each (launch_sc1_round_group: blockIdx.y = proof) with one wait, and the other
 // steps queue the k proofs' launches back to back before one wait. Every value is computed by the same
 // kernels and host formulas as prove(), so each proof's bytes are its own prove()'s.
-std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* Ws, int k, const ProveOpts* os) {
+std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* Ws, int k, const ProveOpts* os,
+                                              std::vector<std::string>* rejected) {
     static_assert(kGroupMax <= 16, "one sumcheck ticket per proof of a group: Ctx::ticket holds 16 counters");
     if (k < 1 || k > kGroupMax) invalid("lockstep group size must be 1.." + std::to_string(kGroupMax));
     CtxClaim claim;
@@ -1794,6 +1878,15 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
             launch_sparse3(0, I.rows.view(), p.z, p.Az, p.Bz, p.Cz, nullptr, nl, I.rows.chunks.as<LongChunk>(),
                            I.rows.nchunks, I.rows.lrows.as<LongRow>(), I.rows.nlrows, p.partial, C.stream);
     }
+    // ---- witness check (off by default): the k proofs' checks in one launch (blockIdx.y = proof); the
+    // records are read behind the group's first wait (round 2's)
+    const bool wcheck = C.witness_check();
+    std::vector<std::string> why(k);
+    if (wcheck) {
+        std::vector<R1csCheckJob> jobs;
+        for (int j = 0; j < k; ++j) jobs.push_back(witness_job(C, j, ps[j].Az, ps[j].Bz, ps[j].Cz, ps[j].partial));
+        witness_check_launch(C, jobs.data(), k, nl, 0);
+    }
     // ---- transcripts: A, B, C (cached or absorbed), v; round 1 with the stubbed commitment
     for (int j = 0; j < k; ++j) {
         P& p = ps[j];
@@ -1844,6 +1937,13 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         }
         open_all(pts);
     }
+    if (wcheck)  // a rejected proof keeps its slot (the group runs on in lockstep); its bytes are dropped at the end
+        for (int j = 0; j < k; ++j) {
+            const WitnessReport rep = witness_verdict(C, j, comm, n);
+            if (!rep.bad) continue;
+            why[j] = rep.message();
+            if (!rejected) throw SpxError(kWrongWitness, why[j]);  // (the stream is idle: open_all waited)
+        }
     // ---- round 3: tau (one copy for the group), eq tables (one launch pair); sumcheck 1 setup
     for (int j = 0; j < k; ++j) {
         P& p = ps[j];
@@ -2107,9 +2207,43 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         open_all(pts);
     }
     std::vector<std::vector<uint8_t>> out(k);
-    for (int j = 0; j < k; ++j) out[j] = std::move(ps[j].proof.b);
+    for (int j = 0; j < k; ++j)
+        if (why[j].empty()) out[j] = std::move(ps[j].proof.b);
+    if (rejected) *rejected = std::move(why);
     C.timings.emplace_back("total_group", tgroup.us());
     return out;
+}
+
+// ====================================================================== stand-alone witness check
+// prove()'s first launch (the index's SpMV, sliced or CSR) into scratch, the check kernel, one wait.
+WitnessReport check_witness(Ctx& C, Index& I, Witness& W) {
+    CtxClaim claim(C);
+    struct UnwindDrain {  // a failed exchange leaves nothing running that reads W.z
+        Ctx& C;
+        int pending = std::uncaught_exceptions();
+        ~UnwindDrain() {
+            if (std::uncaught_exceptions() > pending) (void)hipStreamSynchronize(C.stream);
+        }
+    } drain{C};
+    Comm& comm = *C.comm;
+    const int G = comm.size(), rank = comm.rank();
+    if (G != I.G || rank != I.rank) invalid("index was built for a different communicator");
+    if (W.n != I.n) invalid("|v| + |w| != number of variables");
+    C.side_sync();
+    const uint64_t nl = I.n / G, lo = (uint64_t)rank * nl;
+    const uint64_t npart = std::max<uint64_t>(kRoundPartials, I.rows.nchunks);
+    C.scratch.ensure(32 * (3 * nl + npart));
+    Fr *Az = C.scratch.as<Fr>(), *Bz = Az + nl, *Cz = Bz + nl, *partial = Cz + nl;
+    const Fr* z = W.z.as<Fr>();
+    if (I.rows_sliced.on)
+        launch_spmv_sliced(I.rows_sliced.view(), z, Az, Bz, Cz, I.rows_sliced.entries, C.stream);
+    else
+        launch_sparse3(0, I.rows.view(), z, Az, Bz, Cz, nullptr, nl, I.rows.chunks.as<LongChunk>(), I.rows.nchunks,
+                       I.rows.lrows.as<LongRow>(), I.rows.nlrows, partial, C.stream);
+    const R1csCheckJob job = witness_job(C, 0, Az, Bz, Cz, partial);
+    witness_check_launch(C, &job, 1, nl, lo);
+    C.sync();
+    return witness_verdict(C, 0, comm, I.n);
 }
 
 // ====================================================================== kernel-level entry points

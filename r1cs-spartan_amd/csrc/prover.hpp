@@ -201,7 +201,8 @@ struct Ctx {
     // stream sync that covers the copies issued from it.
     enum : size_t {
         kPinHp = 0,                 // prove(): challenges up, round results down (128 KiB: 8 KiB per proof of a group)
-        kPinCommit = 128 << 10,     // commitment MSM result + status (4 KiB)
+        kPinCommit = 128 << 10,     // commitment MSM result + status (2 KiB)
+        kPinWitness = 130 << 10,    // the witness check's records, one per proof of a group (2 KiB)
         kPinLvl0 = 132 << 10,       // shared level-0 opening proof + status (4 KiB)
         kPinOpen = 136 << 10,       // opening results + status / evaluations (56 KiB)
         kPinStage = 192 << 10,      // small host-to-device staging (opening points, constants, a group's challenges) (128 KiB)
@@ -254,6 +255,13 @@ struct Ctx {
     int subgroup_mode = -1;
     bool subgroup_check() const;
     std::atomic<uint64_t> sgstat[3] = {};
+    // witness check in prove / prove_group: 1 on, 0 off, -1 the process default
+    // (SPX_WITNESS_CHECK=1 -> on, else off); must be equal on every rank of a communicator (the setter
+    // clears knobs_agreed). Counters, cumulative: witnesses checked, witnesses rejected, check launches,
+    // rows checked (local rows, summed over the launches' proofs)
+    int witness_check_mode = -1;
+    bool witness_check() const;
+    std::atomic<uint64_t> wcstat[4] = {};
     Ctx(int dev);
     ~Ctx();
     // region [off, off + bytes) of the pinned carve-out (throws if it does not fit its region)
@@ -427,8 +435,24 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
 // the same steps as prove() for each, with every sumcheck round of the k proofs in one launch and one
 // host wait, and the other steps' launches of the k proofs queued back to back before one wait. Each
 // proof's bytes equal its own prove()'s; o[j] are proof j's options (all stubbed, none interactive).
-std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* W, int k, const ProveOpts* o);
+// With the context's witness check on, a rejected proof keeps its slot to the end (the group is not
+// re-formed) and its bytes are dropped: out[j] is empty and (*rejected)[j] holds its message (empty for
+// the proofs produced). Without `rejected`, the first rejected witness throws kWrongWitness.
+std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* W, int k, const ProveOpts* o,
+                                              std::vector<std::string>* rejected = nullptr);
 size_t proof_size(int log_n);
+
+// Witness check: the constraints x with (Az)[x] (Bz)[x] != (Cz)[x], of the tables the proof
+// is built from (sum_over_y). bad = their number, first_row = the lowest (UINT64_MAX if none), abc = Az,
+// Bz, Cz of that row as canonical Fr.
+struct WitnessReport {
+    uint64_t bad = 0, first_row = ~0ull, rows = 0;
+    uint8_t abc[96] = {};
+    std::string message() const;  // "constraint 37 is not satisfied: (Az)(Bz) != Cz (5 of 256 constraints fail)"
+};
+// Claims the context, runs the index's SpMV and the check kernel, waits once. On a sharded context every
+// rank must call it (one exchange of the ranks' records); every rank gets the same report.
+WitnessReport check_witness(Ctx& C, Index& I, Witness& W);
 
 // verifier (lib.rs:147-212 with verifier.rs:143-512); VerifierParameter: data_structures.rs:19-26
 struct VP {

@@ -8,6 +8,7 @@ REV="$1"; OUT=$(realpath -m "$2"); XF="${3:-}"
 D=$(mktemp -d /tmp/abbuild.XXXXXX)
 git archive "$REV" r1cs-spartan_amd include | tar -x -C "$D"
 mkdir -p "$(dirname "$OUT")"
-make -s -j"${MAX_JOBS:-8}" -C "$D/r1cs-spartan_amd/csrc" OUT="$OUT" OBJDIR="$D/obj" XFLAGS="$XF"
+# (the library alone: the default target also builds the tests' device library, which is not archived)
+make -s -j"${MAX_JOBS:-8}" -C "$D/r1cs-spartan_amd/csrc" OUT="$OUT" OBJDIR="$D/obj" XFLAGS="$XF" "$OUT"
 rm -rf "$D"
 echo "built $REV -> $OUT"
