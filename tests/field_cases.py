@@ -10,7 +10,9 @@ the kernels' formulas. A Suite is one wrapped op with
           a GPU failure is the kernel's and not the input's),
   check   compares the raw device output of one case with the reference; returns None or a message.
 The directed operands sit on the bounds the headers document (ff29.hpp, fq2pair.hpp, curve29.hpp):
-a change to a bound there has to change the tables here with it.
+a change to a bound there has to change the tables here with it. The "xyzz" family is the 32-bit-limb
+XYZZ layer of curve_dev.hpp (preprocessing, keygen, the batch verifier's combinations): canonical
+words in and out, every branch of its formulas named by a tag on the cases aimed at it.
 """
 import itertools
 import random
@@ -685,13 +687,14 @@ def edge_field(F, rng, i):
     return from_dev(F, (pick(i), pick(i * 7 + 3) if i % 3 else 0))
 
 
-def base_points(F, rng, n):
+def base_points(F, rng, n, edge=None):
     """(x, y) with y != 0, on the curve with b = y^2 - x^3: edge device coordinates and random ones"""
+    edge = edge or edge_field
     pts = []
     i = 0
     while len(pts) < n:
         if i < 2 * n // 3:
-            A = (edge_field(F, rng, 5 * i + 1), edge_field(F, rng, 11 * i + 2))
+            A = (edge(F, rng, 5 * i + 1), edge(F, rng, 11 * i + 2))
         else:
             A = (F.from_coeffs([rng.randrange(P) for _ in range(F.deg)]),
                  F.from_coeffs([rng.randrange(1, P) for _ in range(F.deg)]))
@@ -918,6 +921,254 @@ def suitesc():
     return out
 
 
+# ------------------------------------------------------------------ 32-bit-limb XYZZ layer (curve_dev.hpp)
+# One whole point per lane, Montgomery R = 2^384, every coordinate canonical on the way in and on the
+# way out (the 32-bit layer returns canonical words). A case ends with the reference point and a tag
+# naming the branch it is aimed at (tests/test_field_cases.py asserts that every tag is present).
+RQI = pow(RQ, -1, P)
+MUL_SMALL_K = (0, 1, 2, 3, 1 << 31, (1 << 32) - 1)
+
+
+def to_dev32(F, a):
+    return F.from_coeffs([c * RQ % P for c in F.coeffs(a)])
+
+
+def from_dev32(F, v):
+    return F.from_coeffs([c * RQI % P for c in F.coeffs(v)])
+
+
+def aff32(F, A):
+    return (to_dev32(F, A[0]), to_dev32(F, A[1]))
+
+
+def edge_field32(F, rng, i):
+    """field elements whose Montgomery (R = 2^384) form is an edge value of the 12-word layout"""
+    E = [x for x in canon_edges(P, 12) if x]
+    pick = lambda k: E[k % len(E)]
+    if F.deg == 1:
+        return from_dev32(F, pick(i))
+    return from_dev32(F, (pick(i), pick(i * 7 + 3) if i % 3 else 0))
+
+
+def xyzz32(F, A, s):
+    """the representative of the affine point A with ZZ = s^2, ZZZ = s^3 (s != 0)"""
+    s2 = F.mul(s, s)
+    s3 = F.mul(s2, s)
+    return tuple(to_dev32(F, v) for v in (F.mul(A[0], s2), F.mul(A[1], s3), s2, s3))
+
+
+def inf_xyzz32(F, A):
+    """infinity: ZZ == 0 literally; X, Y and ZZZ hold something else (only ZZ may be consulted)"""
+    return aff32(F, A) + (F.zero, to_dev32(F, A[1]))
+
+
+def scalars32(F, rng):
+    """s of the ZZ-scaled representatives: 1 (ZZ = ZZZ = the Montgomery one, as xyzz_from_aff leaves
+    it), small, p - 1, s with an edge Montgomery form, random"""
+    E = [1, 2, P - 1, from_dev32(FQ1, 1), from_dev32(FQ1, P - 1)]
+    if F.deg == 1:
+        return E + [rng.randrange(1, P)]
+    return [(1, 0), (0, E[2]), (E[3], E[4]), (E[1], 0), (rng.randrange(P), rng.randrange(1, P))]
+
+
+def canon32(F, *elems):
+    return all(0 <= c < P for e in elems for c in F.coeffs(e))
+
+
+def fields32(F, o, count):
+    """(the first `count` field elements of the flat word list o, None) or (None, message) if a
+    coefficient is not canonical"""
+    n = 12 * F.deg
+    out = []
+    for k in range(count):
+        cs = [val32(o[n * k + 12 * i:n * k + 12 * i + 12]) for i in range(F.deg)]
+        if any(c >= P for c in cs):
+            return None, "%s not canonical" % ("X", "Y", "ZZ", "ZZZ")[k % 4]
+        out.append(F.from_coeffs(cs))
+    return out, None
+
+
+def check_point32(F, o, want):
+    """o: X, Y, ZZ, ZZZ as flat 32-bit words; want: affine point or INF"""
+    vals, e = fields32(F, o, 4)
+    if e:
+        return e
+    if want is INF:
+        return None if vals[2] == F.zero else "expected infinity as a literal ZZ == 0"
+    X, Y, ZZ, ZZZ = (from_dev32(F, v) for v in vals)
+    if ZZ == F.zero or ZZZ == F.zero:
+        return "unexpected infinity / zero ZZ, ZZZ"
+    if F.mul(F.mul(ZZ, ZZ), ZZ) != F.mul(ZZZ, ZZZ):
+        return "ZZ^3 != ZZZ^2"
+    got = (F.mul(X, F.inv(ZZ)), F.mul(Y, F.inv(ZZZ)))
+    return None if got == (F.red(want[0]), F.red(want[1])) else "affine point differs from the reference"
+
+
+def zmadd_cases(F, n_pts):
+    """(acc, ax, ay, neg, want, tag)"""
+    rng = random.Random(SEED + 71 + F.deg)
+    cases = []
+    for A in base_points(F, rng, n_pts, edge_field32):
+        mult = {k: aff_mul(F, k, A) for k in range(1, 7)}
+        ss = scalars32(F, rng)
+        for t, (k, m) in enumerate(((1, 2), (2, 1), (3, 2), (1, 4), (5, 1))):
+            for neg in (0, 1):
+                B = mult[m]
+                Bin = aff_neg(F, B) if neg else B  # the kernel negates it back
+                acc = xyzz32(F, mult[k], ss[(t + neg) % len(ss)])
+                cases.append((acc,) + aff32(F, Bin) + (neg, aff_add(F, mult[k], B), "generic"))
+        for k in (1, 2):  # P + P and P + (-P), the accumulator in every representative
+            B = mult[k]
+            for s in ss:
+                for neg in (0, 1):
+                    for same in (True, False):
+                        Bk = B if same else aff_neg(F, B)  # what the kernel ends up adding
+                        Bin = aff_neg(F, Bk) if neg else Bk
+                        cases.append((xyzz32(F, B, s),) + aff32(F, Bin) +
+                                     (neg, aff_dbl(F, B) if same else INF, "P + P" if same else "P - P"))
+        for neg in (0, 1):
+            Bin = aff_neg(F, A) if neg else A
+            cases.append((inf_xyzz32(F, mult[2]),) + aff32(F, Bin) + (neg, A, "infinite accumulator"))
+    return cases
+
+
+def zadd_cases(F, n_pts):
+    """(p, q, want, tag)"""
+    rng = random.Random(SEED + 73 + F.deg)
+    cases = []
+    for A in base_points(F, rng, n_pts, edge_field32):
+        mult = {k: aff_mul(F, k, A) for k in range(1, 7)}
+        ss = scalars32(F, rng)
+        for t, (k, m) in enumerate(((1, 2), (2, 1), (3, 2), (1, 4), (5, 1))):
+            p, q = xyzz32(F, mult[k], ss[t % len(ss)]), xyzz32(F, mult[m], ss[(t + 2) % len(ss)])
+            cases.append((p, q, aff_add(F, mult[k], mult[m]), "generic"))
+        for i, s in enumerate(ss):  # equal and opposite points in different representatives
+            for s2 in (s, ss[(i + 1) % len(ss)]):
+                for same in (True, False):
+                    B = mult[2] if same else aff_neg(F, mult[2])
+                    cases.append((xyzz32(F, mult[2], s), xyzz32(F, B, s2), aff_dbl(F, mult[2]) if same else INF,
+                                  "P + P" if same else "P - P"))
+        p = xyzz32(F, mult[3], ss[-1])
+        cases.append((p, inf_xyzz32(F, A), mult[3], "infinite right"))
+        cases.append((inf_xyzz32(F, A), p, mult[3], "infinite left"))
+        cases.append((inf_xyzz32(F, A), inf_xyzz32(F, mult[2]), INF, "both infinite"))
+    return cases
+
+
+def zdbl_cases(F, n_pts):
+    """(p, want, tag)"""
+    rng = random.Random(SEED + 79 + F.deg)
+    cases = []
+    for A in base_points(F, rng, n_pts, edge_field32):
+        for k in (1, 2):
+            B = aff_mul(F, k, A)
+            for s in scalars32(F, rng):
+                cases.append((xyzz32(F, B, s), aff_dbl(F, B), "generic"))
+        cases.append((inf_xyzz32(F, A), INF, "infinity"))
+    return cases
+
+
+def zaff_dbl_cases(F, n_pts):
+    """(ax, ay, want, tag)"""
+    rng = random.Random(SEED + 83 + F.deg)
+    cases = []
+    for A in base_points(F, rng, n_pts, edge_field32):
+        for B in (A, aff_mul(F, 2, A), aff_neg(F, A)):
+            cases.append(aff32(F, B) + (aff_dbl(F, B), "generic"))
+    return cases
+
+
+def zmul_small_cases(F, n_pts):
+    """(p, k, want, tag)"""
+    rng = random.Random(SEED + 89 + F.deg)
+    cases = []
+    pts = base_points(F, rng, 2 * n_pts, edge_field32)
+    done = 0
+    for A in pts:
+        ks = list(MUL_SMALL_K) + [rng.randrange(4, 1 << 32), rng.randrange(4, 1 << 16)]
+        try:  # a multiple of y == 0 on the way (a point of small order on A's own curve): another point
+            want = {k: aff_mul(F, k, A) for k in ks}
+        except (AssertionError, ValueError):
+            continue
+        ss = scalars32(F, rng)
+        for i, k in enumerate(ks):
+            for s in (ss[0], ss[(i + 1) % len(ss)]):
+                cases.append((xyzz32(F, A, s), k, want[k], "k = 0" if k == 0 else "generic"))
+            cases.append((inf_xyzz32(F, A), k, INF, "infinite point"))
+        done += 1
+        if done == n_pts:
+            break
+    assert done == n_pts
+    return cases
+
+
+def zfrom_aff_cases(F, n_pts):
+    """(ax, ay, want, tag): want is the point itself, or INF for the (0, 0) sentinel"""
+    rng = random.Random(SEED + 97 + F.deg)
+    cases = [(F.zero, F.zero, INF, "sentinel")]
+    for A in base_points(F, rng, n_pts, edge_field32):
+        cases.append(aff32(F, A) + (A, "generic"))
+        # one zero coordinate is not the sentinel
+        cases.append((F.zero, to_dev32(F, A[1]), (F.zero, A[1]), "x zero"))
+        cases.append((to_dev32(F, A[0]), F.zero, (A[0], F.zero), "y zero"))
+    if F.deg == 2:  # nor is a single nonzero coefficient anywhere
+        for pos in range(4):
+            v = [0, 0, 0, 0]
+            v[pos] = to_dev32(FQ1, rng.randrange(1, P))
+            x, y = (v[0], v[1]), (v[2], v[3])
+            cases.append((x, y, (from_dev32(F, x), from_dev32(F, y)), "one coefficient"))
+    return cases
+
+
+def chk_zfrom_aff(F, c, o):
+    n = 48 * F.deg
+    flag = int(o[n])
+    if flag != (1 if c[2] is INF else 0):
+        return "xyzz_is_inf gave %d" % flag
+    e = check_point32(F, o[:n], c[2])
+    if e or c[2] is INF:
+        return e
+    vals, _ = fields32(F, o, 4)
+    one = to_dev32(F, F.one)
+    if (vals[0], vals[1]) != (c[0], c[1]) or vals[2] != one or vals[3] != one:
+        return "not the affine point with ZZ = ZZZ = 1"
+
+
+def chk_zdbl(F, c, o):
+    n = 48 * F.deg
+    e = check_point32(F, o[:n], c[1])
+    if e:
+        return "into another point: " + e
+    e = check_point32(F, o[n:], c[1])
+    if e:
+        return "in place: " + e
+
+
+def suitesz():
+    out = []
+    for name, F, base, form in (("Fq", FQ1, 110, "W12"), ("Fq2", FQ2, 120, "W24")):
+        n = 12 if F.deg == 1 else 6
+        pt = lambda p, F=F: canon32(F, *p)
+        out.append(Suite("xyzz_madd<%s>" % name, base, form, zmadd_cases(F, n),
+                         lambda c, F=F, pt=pt: (pt(c[0]) and canon32(F, c[1], c[2]) and c[3] in (0, 1) and
+                                                (c[1], c[2]) != (F.zero, F.zero)),  # xyzz_madd takes no infinity
+                         lambda c, o, F=F: check_point32(F, o, c[4]), operands=lambda c: [c[0], c[1], c[2], ("w", c[3])]))
+        out.append(Suite("xyzz_add<%s>" % name, base + 1, form, zadd_cases(F, n), lambda c, pt=pt: pt(c[0]) and pt(c[1]),
+                         lambda c, o, F=F: check_point32(F, o, c[2]), operands=lambda c: list(c[:2])))
+        out.append(Suite("xyzz_dbl<%s>" % name, base + 2, form, zdbl_cases(F, n), lambda c, pt=pt: pt(c[0]),
+                         lambda c, o, F=F: chk_zdbl(F, c, o), operands=lambda c: [c[0]]))
+        out.append(Suite("xyzz_from_aff_dbl<%s>" % name, base + 3, form, zaff_dbl_cases(F, n),
+                         lambda c, F=F: canon32(F, c[0], c[1]) and c[1] != F.zero,
+                         lambda c, o, F=F: check_point32(F, o, c[2]), operands=lambda c: list(c[:2])))
+        out.append(Suite("xyzz_mul_small<%s>" % name, base + 4, form, zmul_small_cases(F, n // 2),
+                         lambda c, pt=pt: pt(c[0]) and 0 <= c[1] < 1 << 32,
+                         lambda c, o, F=F: check_point32(F, o, c[2]), operands=lambda c: [c[0], ("w", c[1])]))
+        out.append(Suite("xyzz_from_aff_is_inf<%s>" % name, base + 5, form, zfrom_aff_cases(F, n),
+                         lambda c, F=F: canon32(F, c[0], c[1]),
+                         lambda c, o, F=F: chk_zfrom_aff(F, c, o), operands=lambda c: list(c[:2])))
+    return out
+
+
 # ------------------------------------------------------------------ lane layout
 def lanes_per_element(form):
     return 2 if form == "PAIR" else 1
@@ -965,7 +1216,7 @@ def decode(suite, rows):
     return [[r[14 * k:14 * k + 14]] for k in range(4)]
 
 
-FAMILIES = {"limb32": suites32, "f29": suites29, "fq2": suitesq, "curve": suitesc}
+FAMILIES = {"limb32": suites32, "f29": suites29, "fq2": suitesq, "curve": suitesc, "xyzz": suitesz}
 # the suites of each family by name (the GPU test is parametrised over these without generating the
 # cases at collection time; tests/test_field_cases.py checks that the lists match)
 NAMES = {
@@ -979,6 +1230,8 @@ NAMES = {
     "curve": ["x29_madd<F29>", "x29_from_aff_dbl<F29>", "x29_add<F29>", "x29_dbl<F29>", "x29_madd<FP29A>",
               "x29_from_aff_dbl<FP29A>", "x29_add<FP29A>", "x29_dbl<FP29A>", "x29_add_split<F29>",
               "x29_dbl_split<F29>", "x29_add_split<FP29>", "x29_dbl_split<FP29>"],
+    "xyzz": [s + "<%s>" % f for f in ("Fq", "Fq2")
+             for s in ("xyzz_madd", "xyzz_add", "xyzz_dbl", "xyzz_from_aff_dbl", "xyzz_mul_small", "xyzz_from_aff_is_inf")],
 }
 _cache = {}
 

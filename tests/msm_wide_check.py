@@ -5,7 +5,8 @@ loaded and a public parameter is preprocessed.
 
   msm_wide_check.py msm
       msm_g1 / msm_g2 at n = 2^10 against the oracle: random scalars with the edge scalars of the
-      recoding among them, and one scalar n times (hot buckets). The same equal-scalar case at
+      recoding among them (also with every third base at infinity), and one scalar n times (hot
+      buckets). The same equal-scalar case at
       n = 2^12 with every digit 1: bucket 0 takes 15 x 2^12 references, more than the bin staging
       of the sort (kBinStage = 36864; 15 x 2^10 cannot reach it).
   msm_wide_check.py proof DIR G EXPECT [reruns]
@@ -108,23 +109,30 @@ def run_msm(spx, oc):
     ctx = spx.Context(0)
     g1, g2 = pp_bases(spx.MLProofForR1CS.setup(ctx, LOG_N, PP_SEED).serialize_uncompressed(), LOG_N)
     assert spx.msm_window_plan(1 << 10) == (17, 15) and spx.msm_window_plan(1 << 9)[0] < 16
+    from bls12_381 import g1_uncompressed, g2_uncompressed
+
     fails = []
-    cases = [("edge + random", 10, edge_and_random(1 << 10, 21)),
-             ("one scalar n times", 10, fr([FIXED]) * (1 << 10)),
-             ("every digit 1, n times", 12, fr([from_windows([1] * W)]) * (1 << 12))]
-    for name, lg, sc in cases:
+    cases = [("edge + random", 10, edge_and_random(1 << 10, 21), 0),
+             ("one scalar n times", 10, fr([FIXED]) * (1 << 10), 0),
+             ("every digit 1, n times", 12, fr([from_windows([1] * W)]) * (1 << 12), 0),
+             # finite and infinite references in one wave, under folded digits (flipped reference signs)
+             ("edge + random, every third base infinite", 10, edge_and_random(1 << 10, 22), 3)]
+    for name, lg, sc, inf_every in cases:
         n = 1 << lg
         b1, b2 = g1[: 96 * n], g2[: 192 * n]
+        if inf_every:
+            b1 = b"".join(g1_uncompressed(None) if i % inf_every == 0 else b1[96 * i : 96 * (i + 1)] for i in range(n))
+            b2 = b"".join(g2_uncompressed(None) if i % inf_every == 0 else b2[192 * i : 192 * (i + 1)] for i in range(n))
         before = ctx.msm_skew_stats()
         for grp, got, want in (("g1", spx.msm_g1(ctx, b1, sc), oc.msm_g1(b1, sc, n)),
                                ("g2", spx.msm_g2(ctx, b2, sc), oc.msm_g2(b2, sc, n))):
             ok = got == want
-            print("%-24s 2^%d %s %s" % (name, lg, grp, "ok" if ok else "DIFFERS"), flush=True)
+            print("%-40s 2^%d %s %s" % (name, lg, grp, "ok" if ok else "DIFFERS"), flush=True)
             if not ok:
                 fails.append((name, grp))
         st = ctx.msm_skew_stats()
         print("skew stats", st, flush=True)
-        if name != "edge + random" and st[2] <= before[2]:
+        if not name.startswith("edge + random") and st[2] <= before[2]:
             fails.append((name, "no hot bucket reduced", st))
     print("FAILED: %s" % fails if fails else "all equal", flush=True)
     return 1 if fails else 0

@@ -1,5 +1,5 @@
 // Test-only device library: one thin __global__ wrapper per field / curve device function of
-// ff_dev.hpp, ff29.hpp, fq2pair.hpp, curve29.hpp and the split additions of msm_impl.hpp, so that
+// ff_dev.hpp, ff29.hpp, fq2pair.hpp, curve29.hpp, curve_dev.hpp and the split additions of msm_impl.hpp, so that
 // tests/test_gpu_field_ops.py can feed each of them chosen operands (tests/field_cases.py) and read
 // the raw result. Nothing here is part of libspartan_hip.so and nothing depends on it.
 //
@@ -429,6 +429,96 @@ struct OpDbl {
     }
 };
 
+// ---------------------------------------------------------------- 32-bit-limb XYZZ layer (curve_dev.hpp)
+// one whole point per lane (F = Fq: 12 words per coordinate, Fq2: 24), Montgomery R = 2^384, canonical
+template <class F>
+DEV void ldz(Xyzz<F>& p, const uint32_t* in) {
+    constexpr int W = Io<F>::W;
+    Io<F>::ld(p.x, in);
+    Io<F>::ld(p.y, in + W);
+    Io<F>::ld(p.zz, in + 2 * W);
+    Io<F>::ld(p.zzz, in + 3 * W);
+}
+template <class F>
+DEV void stz(uint32_t* out, const Xyzz<F>& p) {
+    constexpr int W = Io<F>::W;
+    Io<F>::st(out, p.x);
+    Io<F>::st(out + W, p.y);
+    Io<F>::st(out + 2 * W, p.zz);
+    Io<F>::st(out + 3 * W, p.zzz);
+}
+template <class F>
+struct OpZMadd {  // acc (X, Y, ZZ, ZZZ), ax, ay, neg -> acc
+    static constexpr int W = Io<F>::W, NI = 6 * W + 1, NO = 4 * W;
+    static DEV void run(const uint32_t* in, uint32_t* out) {
+        Xyzz<F> p;
+        Aff<F> a;
+        ldz(p, in);
+        Io<F>::ld(a.x, in + 4 * W);
+        Io<F>::ld(a.y, in + 5 * W);
+        xyzz_madd(p, a, in[6 * W] != 0);
+        stz(out, p);
+    }
+};
+template <class F>
+struct OpZAdd {  // p, q -> p + q
+    static constexpr int W = Io<F>::W, NI = 8 * W, NO = 4 * W;
+    static DEV void run(const uint32_t* in, uint32_t* out) {
+        Xyzz<F> p, q;
+        ldz(p, in);
+        ldz(q, in + 4 * W);
+        xyzz_add(p, q);
+        stz(out, p);
+    }
+};
+template <class F>
+struct OpZDbl {  // p -> 2p into another point, 2p in place (as every caller in the library uses it)
+    static constexpr int W = Io<F>::W, NI = 4 * W, NO = 8 * W;
+    static DEV void run(const uint32_t* in, uint32_t* out) {
+        Xyzz<F> p, r;
+        ldz(p, in);
+        xyzz_dbl(r, p);
+        stz(out, r);
+        xyzz_dbl(p, p);
+        stz(out + 4 * W, p);
+    }
+};
+template <class F>
+struct OpZAffDbl {  // ax, ay -> 2a
+    static constexpr int W = Io<F>::W, NI = 2 * W, NO = 4 * W;
+    static DEV void run(const uint32_t* in, uint32_t* out) {
+        Xyzz<F> r;
+        Aff<F> a;
+        Io<F>::ld(a.x, in);
+        Io<F>::ld(a.y, in + W);
+        xyzz_from_aff_dbl(r, a);
+        stz(out, r);
+    }
+};
+template <class F>
+struct OpZMulSmall {  // p, k -> k p
+    static constexpr int W = Io<F>::W, NI = 4 * W + 1, NO = 4 * W;
+    static DEV void run(const uint32_t* in, uint32_t* out) {
+        Xyzz<F> p, r;
+        ldz(p, in);
+        xyzz_mul_small(r, p, in[4 * W]);
+        stz(out, r);
+    }
+};
+template <class F>
+struct OpZFromAff {  // ax, ay (the (0, 0) sentinel: infinity) -> point, xyzz_is_inf(point)
+    static constexpr int W = Io<F>::W, NI = 2 * W, NO = 4 * W + 1;
+    static DEV void run(const uint32_t* in, uint32_t* out) {
+        Xyzz<F> r;
+        Aff<F> a;
+        Io<F>::ld(a.x, in);
+        Io<F>::ld(a.y, in + W);
+        xyzz_from_aff(r, a);
+        stz(out, r);
+        out[4 * W] = xyzz_is_inf(r) ? 1u : 0u;
+    }
+};
+
 template <class Op>
 __global__ __launch_bounds__(64) void k_op(const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
     const size_t lane = blockIdx.x * (size_t)64 + threadIdx.x;
@@ -476,6 +566,18 @@ int run_c(int sub, const uint32_t* in, uint32_t* out, uint64_t lanes, int* ni, i
         case 1: return run_op<OpAffDbl<F>>(in, out, lanes, ni, no);
         case 2: return run_op<OpAdd<F, false>>(in, out, lanes, ni, no);
         case 3: return run_op<OpDbl<F, false>>(in, out, lanes, ni, no);
+    }
+    return -2;
+}
+template <class F>
+int run_z(int sub, const uint32_t* in, uint32_t* out, uint64_t lanes, int* ni, int* no) {
+    switch (sub) {
+        case 0: return run_op<OpZMadd<F>>(in, out, lanes, ni, no);
+        case 1: return run_op<OpZAdd<F>>(in, out, lanes, ni, no);
+        case 2: return run_op<OpZDbl<F>>(in, out, lanes, ni, no);
+        case 3: return run_op<OpZAffDbl<F>>(in, out, lanes, ni, no);
+        case 4: return run_op<OpZMulSmall<F>>(in, out, lanes, ni, no);
+        case 5: return run_op<OpZFromAff<F>>(in, out, lanes, ni, no);
     }
     return -2;
 }
@@ -527,6 +629,8 @@ extern "C" int spx_field_op(int op, const uint32_t* in, uint32_t* out, uint64_t 
         case 101: return run_op<OpDbl<F29, true>>(in, out, lanes, ni, no);
         case 102: return run_op<OpAdd<FP29, true>>(in, out, lanes, ni, no);
         case 103: return run_op<OpDbl<FP29, true>>(in, out, lanes, ni, no);
+        case 110: case 111: case 112: case 113: case 114: case 115: return run_z<Fq>(op - 110, in, out, lanes, ni, no);
+        case 120: case 121: case 122: case 123: case 124: case 125: return run_z<Fq2>(op - 120, in, out, lanes, ni, no);
     }
     return -2;
 }

@@ -4,6 +4,7 @@ the kernel's and not the input's), the curve reference agrees with the oracle on
 the Montgomery constants in the headers equal values recomputed from p and r, and the test-only
 device library compiles for gfx950."""
 import os
+import random
 import re
 import shutil
 import subprocess
@@ -126,6 +127,85 @@ def test_checkers_reject_wrong_results():
     assert m.check(c, o)
     inf = next(c for c in m.cases if c[4] is fc.INF)
     assert m.check(inf, o)
+
+
+XYZZ_TAGS = {
+    "xyzz_madd": {"generic", "P + P", "P - P", "infinite accumulator"},
+    "xyzz_add": {"generic", "P + P", "P - P", "infinite left", "infinite right", "both infinite"},
+    "xyzz_dbl": {"generic", "infinity"},
+    "xyzz_from_aff_dbl": {"generic"},
+    "xyzz_mul_small": {"generic", "k = 0", "infinite point"},
+    "xyzz_from_aff_is_inf": {"generic", "sentinel", "x zero", "y zero"},
+}
+
+
+@pytest.mark.parametrize("field", ["Fq", "Fq2"])
+def test_xyzz_case_tables_reach_every_branch(field):
+    """the 32-bit XYZZ family: every branch of curve_dev.hpp's formulas has cases aimed at it, with the
+    reference result that branch must give; xyzz_madd runs with neg false and true in each of them; the
+    equal / opposite points come in several ZZ-scaled representatives; xyzz_mul_small gets every
+    directed k with a finite and with an infinite point"""
+    F = fc.FQ1 if field == "Fq" else fc.FQ2
+    for op, tags in XYZZ_TAGS.items():
+        s = fc.suite("xyzz", "%s<%s>" % (op, field))
+        assert {c[-1] for c in s.cases} == tags | ({"one coefficient"} if (op, field) == ("xyzz_from_aff_is_inf", "Fq2") else set())
+        for c in s.cases:
+            want, tag = c[-2], c[-1]
+            if tag in ("P - P", "both infinite", "infinity", "k = 0", "infinite point", "sentinel"):
+                assert want is fc.INF, (op, tag)
+            else:
+                assert want is not fc.INF, (op, tag)
+    m = fc.suite("xyzz", "xyzz_madd<%s>" % field)
+    assert {(c[5], c[3]) for c in m.cases} == {(t, n) for t in XYZZ_TAGS["xyzz_madd"] for n in (0, 1)}
+    for s, tag in ((m, "P + P"), (m, "P - P"), (fc.suite("xyzz", "xyzz_add<%s>" % field), "P + P")):
+        assert len({c[0][2] for c in s.cases if c[-1] == tag}) >= 5  # distinct ZZ of the first operand
+    for c in m.cases:  # the accumulator really is a representative of the point the tag speaks of
+        if c[5] in ("P + P", "P - P"):
+            X, Y, ZZ, ZZZ = (fc.from_dev32(F, v) for v in c[0])
+            a = (fc.from_dev32(F, c[1]), fc.from_dev32(F, c[2]))
+            if c[3]:
+                a = fc.aff_neg(F, a)
+            assert F.mul(a[0], ZZ) == X
+            assert F.mul(a[1], ZZZ) == (Y if c[5] == "P + P" else F.neg(Y))
+    ms = fc.suite("xyzz", "xyzz_mul_small<%s>" % field)
+    for inf in (False, True):
+        assert {c[1] for c in ms.cases if (c[0][2] == F.zero) == inf} >= set(fc.MUL_SMALL_K)
+    for c in fc.suite("xyzz", "xyzz_add<%s>" % field).cases:
+        assert (c[0][2] == F.zero) == (c[3] in ("infinite left", "both infinite"))
+        assert (c[1][2] == F.zero) == (c[3] in ("infinite right", "both infinite"))
+
+
+@pytest.mark.parametrize("field", ["Fq", "Fq2"])
+def test_xyzz_checker_accepts_the_reference_and_rejects_wrong_points(field):
+    F = fc.FQ1 if field == "Fq" else fc.FQ2
+    m = fc.suite("xyzz", "xyzz_madd<%s>" % field)
+    flat = lambda pt: [w for e in pt for cf in F.coeffs(e) for w in fc.words(cf, 12)]
+    c = next(c for c in m.cases if c[5] == "generic")
+    s = fc.scalars32(F, random.Random(1))[2]
+    assert m.check(c, flat(fc.xyzz32(F, c[4], F.one))) is None
+    assert m.check(c, flat(fc.xyzz32(F, c[4], s))) is None  # any representative of the right point
+    good = fc.xyzz32(F, c[4], s)
+    assert m.check(c, flat(fc.xyzz32(F, fc.aff_neg(F, c[4]), s)))  # the wrong point
+    assert m.check(c, flat(good[:2] + (F.zero, good[3])))  # infinity where a point is due
+    assert m.check(c, flat(good[:3] + (fc.to_dev32(F, F.one),)))  # ZZ^3 != ZZZ^2
+    noncanon = flat(good)
+    noncanon[:12] = fc.words(F.coeffs(good[0])[0] + P, 12)  # the same value, one p higher
+    assert m.check(c, noncanon) == "X not canonical"
+    inf = next(c for c in m.cases if c[5] == "P - P")
+    assert m.check(inf, flat(good))  # a point where infinity is due
+    assert m.check(inf, flat(good[:2] + (F.zero, F.zero))) is None
+    f = fc.suite("xyzz", "xyzz_from_aff_is_inf<%s>" % field)
+    sen = next(c for c in f.cases if c[3] == "sentinel")
+    one = fc.to_dev32(F, F.one)
+    assert f.check(sen, flat((one, one, F.zero, F.zero)) + [1]) is None
+    assert f.check(sen, flat((one, one, F.zero, F.zero)) + [0])
+    g = next(c for c in f.cases if c[3] == "x zero")
+    assert f.check(g, flat((g[0], g[1], one, one)) + [0]) is None
+    assert f.check(g, flat((one, one, F.zero, F.zero)) + [1])  # taken for the sentinel
+    d = fc.suite("xyzz", "xyzz_dbl<%s>" % field)
+    c = next(c for c in d.cases if c[2] == "generic")
+    ok, bad = flat(fc.xyzz32(F, c[1], s)), flat(fc.xyzz32(F, fc.aff_neg(F, c[1]), s))
+    assert d.check(c, ok + ok) is None and d.check(c, ok + bad) and d.check(c, bad + ok)
 
 
 # ------------------------------------------------------------------ header constants

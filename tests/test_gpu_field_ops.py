@@ -1,9 +1,10 @@
 """The device field and curve functions, one at a time, against big-integer references at the operands
 where their bound arguments are tight (tests/field_cases.py). tests/native/field_ops.hip wraps each
-inline function of ff_dev.hpp / ff_asm.hpp (32-bit limbs), ff29.hpp, fq2pair.hpp, curve29.hpp and the
-split additions of msm_impl.hpp in a kernel of its own; the product library is not involved.
+inline function of ff_dev.hpp / ff_asm.hpp (32-bit limbs), ff29.hpp, fq2pair.hpp, curve29.hpp, curve_dev.hpp
+(the 32-bit-limb XYZZ formulas) and the split additions of msm_impl.hpp in a kernel of its own; the
+product library is not involved.
 
-32-bit layer: exact word equality. Radix-2^29 layer: a rewrite may return another representative, so
+32-bit layer: exact word equality; its XYZZ points: canonical words, the reference point. Radix-2^29 layer: a rewrite may return another representative, so
 the assertions are congruence mod p, the value bound the header documents for the op, and normalized
 limbs; predicates and infinity (a literal ZZ == 0) are exact. The bound comments of ff29.hpp,
 fq2pair.hpp and curve29.hpp are what the case tables encode: change a bound there and the table
@@ -118,6 +119,16 @@ def test_curve_formulas(lib, name):
     """x29_madd / x29_from_aff_dbl / x29_add / x29_dbl and the split forms against textbook affine
     arithmetic: generic, P + P through every representative, P + (-P), infinity on either side"""
     run_suite(lib, fc.suite("curve", name))
+
+
+@pytest.mark.parametrize("name", fc.NAMES["xyzz"])
+def test_xyzz32_layer(lib, name):
+    """curve_dev.hpp over Fq and Fq2 (32-bit limbs): xyzz_madd (neg false / true), xyzz_add, xyzz_dbl (into
+    another point and in place), xyzz_from_aff_dbl, xyzz_mul_small (k = 0, 1, 2, 3, 2^31, 2^32 - 1),
+    xyzz_from_aff with xyzz_is_inf, against textbook affine arithmetic: generic, P + P and P + (-P) through
+    several ZZ-scaled representatives, infinity on either side, the (0, 0) sentinel. Exact: infinity is
+    a literal ZZ == 0, otherwise (X / ZZ, Y / ZZZ) is the reference point, ZZ^3 == ZZZ^2, canonical words"""
+    run_suite(lib, fc.suite("xyzz", name))
 
 
 def test_regression_fr_inv_exponent_borrow(lib):

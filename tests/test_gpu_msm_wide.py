@@ -45,8 +45,8 @@ def ref(spx, ctx, oc, tmp_path_factory):
 @pytest.mark.parametrize("form", ["auto", "staged", "direct"])
 def test_msm_edge_scalars(form):
     """msm_g1 / msm_g2 at n = 2^10: random scalars with 0, 1, r - 1, (r - 1) / 2, (r + 1) / 2, the largest
-    top digit, the carry through every window, the 2^16 tie and their negatives among them; one scalar
-    n times (hot buckets); every digit 1 at n = 2^12 (a bin above the sort's staging). By the sort's
+    top digit, the carry through every window, the 2^16 tie and their negatives among them, with finite
+    bases and with every third base at infinity; one scalar n times (hot buckets); every digit 1 at n = 2^12 (a bin above the sort's staging). By the sort's
     own choice of form, and under each forced form."""
     env = {} if form == "auto" else {"SPX_SORT_FORM": form}
     _child(["msm"], SPX_MSM_WIDE_MIN_LOG="10", **env)

@@ -88,8 +88,10 @@ def test_msm_repeated_bases_doubling_and_cancellation(spx, ctx, oc, group):
         assert spx.msm_g2(ctx, b, c) == oc.msm_g2(b, c, n)
 
 
-@pytest.mark.parametrize("nv", [3, 6])
+@pytest.mark.parametrize("nv", [1, 2, 3, 6, 9])
 def test_keygen_matches_oracle(spx, ctx, oc, nv):
+    """2^(nv + 1) - 2 points per curve through k_fixed_base / k_normalize: 2 (the smallest chunk of the
+    batch inversion) up to 1022 (several blocks of 64 threads, a ragged last chunk of 32)"""
     pp = spx.MLProofForR1CS.setup(ctx, nv, 4242)
     assert pp.serialize_uncompressed() == oc.PP.keygen(nv, 4242).serialize()
 
