@@ -148,6 +148,10 @@ DEV void x29_dbl(X29<F>& p) {
 // exits skip the conditional subtractions; every other formula and the packed storage (8p < 2^384)
 // accept loose inputs, because they use X and Y only as product operands (x29_add, x29_dbl:
 // 2Y < 8p) or map them through a product (k_tree_out).
+// The formula's products come in independent pairs (U2 and S2, P^2 and R^2, PPP and Q, ZZ3 and
+// ZZZ3); each pair goes to one routine (mul_x2 / sqr_x2), which the accumulation's field forms
+// reduce in lockstep with seeded carries (ff29.hpp, f29_redc_scan_x2). Same values and bounds as
+// the single products.
 template <class F>
 DEV void x29_madd(X29<F>& p, const F& ax, const F& ay_in, bool neg) {
     using O = Ops29<F>;
@@ -165,8 +169,7 @@ DEV void x29_madd(X29<F>& p, const F& ax, const F& ay_in, bool neg) {
         return;
     }
     F U2, S2, P, R;
-    O::mul(U2, ax, p.zz);
-    O::mul(S2, ay, p.zzz);
+    O::mul_x2(U2, ax, p.zz, S2, ay, p.zzz);
     O::template sub<8>(P, U2, p.x);  // < 10p
     O::template sub<4>(R, S2, p.y);  // < 6p
     if (O::template zero_lt<16>(P)) {
@@ -177,10 +180,8 @@ DEV void x29_madd(X29<F>& p, const F& ax, const F& ay_in, bool neg) {
         return;
     }
     F PP, PPP, Q, t, w;
-    O::template sqr_b<16>(PP, P);    // P.c1 < 10p
-    O::mul(PPP, P, PP);
-    O::mul(Q, p.x, PP);
-    O::sqr(t, R);                    // R.c1 < 6p
+    O::template sqr_x2<16, 8>(PP, P, t, R);  // P.c1 < 10p, R.c1 < 6p
+    O::mul_x2(PPP, P, PP, Q, p.x, PP);
     O::template sub<2>(w, t, PPP);   // < 4p
     O::add(t, Q, Q);                 // < 4p
     O::template sub<4>(w, w, t);     // X3 < 8p (loose)
@@ -191,8 +192,7 @@ DEV void x29_madd(X29<F>& p, const F& ax, const F& ay_in, bool neg) {
     O::template sub<4>(S2, S2, p.y);  // 4p - Y1 (Y1 < 4p), < 4p
     O::mul_sum(p.y, t, R, S2, PPP);   // Y3 < 4p (loose)
     p.x = w;
-    O::mul(p.zz, p.zz, PP);
-    O::mul(p.zzz, p.zzz, PPP);
+    O::mul_x2(p.zz, p.zz, PP, p.zzz, p.zzz, PPP);
 }
 
 // p += q, add-2008-s

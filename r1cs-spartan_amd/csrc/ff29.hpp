@@ -171,6 +171,122 @@ DEV void f29_mul2(F29& r, const F29& a, const F29& b, const F29& c, const F29& d
     f29_redc_sum<2>(r, pa, pb);
 }
 
+// Two independent reductions in lockstep: r0 = REDC(sum a0_j b0_j), r1 = REDC(sum a1_j b1_j), the same
+// words as two f29_redc_sum<NP>, with the carry SEEDED: a column's chain starts at the previous
+// column's carry (the addend of its first v_mad_u64_u32) instead of at 0, so no 64-bit add joins
+// the carry afterwards (one two-slot instruction per column, tools/ubench_issue.hip). A seeded
+// column cannot start before the previous one ends, so a lone seeded reduction is one serial chain
+// of multiply-adds, each waiting for the one before it, and measured slower than the joined form
+// (DESIGN.md 4.1). Two reductions column by column, term by term, give each wave two independent
+// chains to issue from; the mixed addition's products come in such pairs (curve29.hpp, x29_madd).
+// Every partial sum stays behind f29_opaque: LLVM's reassociation orders a sum's terms by how late
+// they are defined, so it would sum the early products from 0 again and join the carry with the
+// 64-bit add. The barrier is no instruction.
+// Bounds per reduction as f29_redc_sum plus the carry: a column < 2^64 leaves a carry < 2^35, and
+// 56 x 2^58 (products and m p, one factor of one product with 2^30 limbs) + 2^35 < 2^64.
+// prod2(k, x0, x1) adds column k's products to both sums, alternating between them.
+template <class Prod2>
+DEV void f29_redc_scan_x2(F29& r0, F29& r1, const Prod2& prod2) {
+    uint32_t m0[14], t0[14], m1[14], t1[14];
+    uint64_t c0 = 0, c1 = 0;
+#pragma unroll
+    for (int k = 0; k < 27; ++k) {
+        const int lo = k < 14 ? 0 : k - 13;
+        uint64_t x0 = c0, x1 = c1;
+        prod2(k, x0, x1);
+#pragma unroll
+        for (int i = lo; i <= (k < 14 ? k - 1 : 13); ++i) {
+            x0 = f29_opaque(x0 + (uint64_t)m0[i] * Q29::P[k - i]);
+            x1 = f29_opaque(x1 + (uint64_t)m1[i] * Q29::P[k - i]);
+        }
+        if (k < 14) {
+            m0[k] = ((uint32_t)x0 * Q29::PINV) & Q29::M;
+            m1[k] = ((uint32_t)x1 * Q29::PINV) & Q29::M;
+            x0 += (uint64_t)m0[k] * Q29::P[0];
+            x1 += (uint64_t)m1[k] * Q29::P[0];
+        } else {
+            t0[k - 14] = (uint32_t)x0 & Q29::M;
+            t1[k - 14] = (uint32_t)x1 & Q29::M;
+        }
+        c0 = x0 >> 29;
+        c1 = x1 >> 29;
+    }
+    t0[13] = (uint32_t)c0;
+    t1[13] = (uint32_t)c1;
+#pragma unroll
+    for (int i = 0; i < 14; ++i) {
+        r0.v[i] = t0[i];
+        r1.v[i] = t1[i];
+    }
+}
+template <int NP>
+DEV void f29_redc_sum_x2(F29& r0, F29& r1, const F29* const (&a0)[NP], const F29* const (&b0)[NP],
+                         const F29* const (&a1)[NP], const F29* const (&b1)[NP]) {
+    f29_redc_scan_x2(r0, r1, [&](int k, uint64_t& x0, uint64_t& x1) {
+        const int lo = k < 14 ? 0 : k - 13, hi = k < 14 ? k : 13;
+#pragma unroll
+        for (int i = lo; i <= hi; ++i) {
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                x0 = f29_opaque(x0 + (uint64_t)a0[q]->v[i] * b0[q]->v[k - i]);
+                x1 = f29_opaque(x1 + (uint64_t)a1[q]->v[i] * b1[q]->v[k - i]);
+            }
+        }
+    });
+}
+// r0 = REDC(a0 a0), r1 = REDC(a1 a1) in lockstep, the same words as f29_mul(r, a, a), each in 105 limb
+// products instead of 196: column k is the sum over i < k - i of a_i (2 a_{k-i}) plus a_{k/2}^2 for
+// even k, the same integer as the full sum. (In f29_mul(r, a, a) the compiler finds the equal
+// products itself; behind the barriers it cannot.) PRECONDITION: limbs normalized (< 2^29; every F29
+// outside the lane-pair operand preparation is), so 2 a_j < 2^30 and a column holds at most 7 cross
+// terms < 2^59 and one square < 2^58: 15 x 2^58 before m p.
+DEV void f29_sqr_x2(F29& r0, const F29& a0, F29& r1, const F29& a1) {
+    uint32_t d0[14], d1[14];
+#pragma unroll
+    for (int i = 0; i < 14; ++i) {
+        d0[i] = a0.v[i] << 1;
+        d1[i] = a1.v[i] << 1;
+    }
+    F29 x, y;
+    f29_redc_scan_x2(x, y, [&](int k, uint64_t& x0, uint64_t& x1) {
+        const int lo = k < 14 ? 0 : k - 13;
+        if (k % 2 == 0) {
+            x0 = f29_opaque(x0 + (uint64_t)a0.v[k / 2] * a0.v[k / 2]);
+            x1 = f29_opaque(x1 + (uint64_t)a1.v[k / 2] * a1.v[k / 2]);
+        }
+#pragma unroll
+        for (int i = lo; 2 * i < k; ++i) {
+            x0 = f29_opaque(x0 + (uint64_t)a0.v[i] * d0[k - i]);
+            x1 = f29_opaque(x1 + (uint64_t)a1.v[i] * d1[k - i]);
+        }
+    });
+    r0 = x;
+    r1 = y;
+}
+// r0 = REDC(a0 b0), r1 = REDC(a1 b1)
+DEV void f29_mul_x2(F29& r0, const F29& a0, const F29& b0, F29& r1, const F29& a1, const F29& b1) {
+    const F29* const pa0[1] = {&a0};
+    const F29* const pb0[1] = {&b0};
+    const F29* const pa1[1] = {&a1};
+    const F29* const pb1[1] = {&b1};
+    F29 x, y;
+    f29_redc_sum_x2<1>(x, y, pa0, pb0, pa1, pb1);
+    r0 = x;
+    r1 = y;
+}
+// r0 = REDC(a0 b0 + c0 d0), r1 = REDC(a1 b1 + c1 d1)
+DEV void f29_mul2_x2(F29& r0, const F29& a0, const F29& b0, const F29& c0, const F29& d0, F29& r1, const F29& a1,
+                     const F29& b1, const F29& c1, const F29& d1) {
+    const F29* const pa0[2] = {&a0, &c0};
+    const F29* const pb0[2] = {&b0, &d0};
+    const F29* const pa1[2] = {&a1, &c1};
+    const F29* const pb1[2] = {&b1, &d1};
+    F29 x, y;
+    f29_redc_sum_x2<2>(x, y, pa0, pb0, pa1, pb1);
+    r0 = x;
+    r1 = y;
+}
+
 DEV void f29_add(F29& r, const F29& a, const F29& b) {
     uint32_t c = 0;
 #pragma unroll
@@ -318,6 +434,14 @@ struct Ops29<F29> {
     // r = a b + c d with one reduction (operands < 16p: the sum < 512 p^2 < 2^406 p), < 2p
     static DEV void mul_sum(F29& r, const F29& a, const F29& b, const F29& c, const F29& d) { f29_mul2(r, a, b, c, d); }
     static DEV void sqr(F29& r, const F29& a) { f29_mul(r, a, a); }
+    // two independent products / squares in lockstep (f29_redc_scan_x2)
+    static DEV void mul_x2(F29& r0, const F29& a0, const F29& b0, F29& r1, const F29& a1, const F29& b1) {
+        f29_mul_x2(r0, a0, b0, r1, a1, b1);
+    }
+    template <int K0, int K1>
+    static DEV void sqr_x2(F29& r0, const F29& a0, F29& r1, const F29& a1) {
+        f29_sqr_x2(r0, a0, r1, a1);
+    }
     static DEV void add(F29& r, const F29& a, const F29& b) { f29_add(r, a, b); }
     template <int K>
     static DEV void sub(F29& r, const F29& a, const F29& b) {
@@ -353,6 +477,15 @@ struct Ops29<F2_29> {
         f29_add(r.c1, x.c1, y.c1);
     }
     static DEV void sqr(F2_29& r, const F2_29& a) { f2_29_sqr(r, a); }
+    static DEV void mul_x2(F2_29& r0, const F2_29& a0, const F2_29& b0, F2_29& r1, const F2_29& a1, const F2_29& b1) {
+        f2_29_mul(r0, a0, b0);
+        f2_29_mul(r1, a1, b1);
+    }
+    template <int K0, int K1>
+    static DEV void sqr_x2(F2_29& r0, const F2_29& a0, F2_29& r1, const F2_29& a1) {
+        f2_29_sqr<K0>(r0, a0);
+        f2_29_sqr<K1>(r1, a1);
+    }
     static DEV void add(F2_29& r, const F2_29& a, const F2_29& b) {
         f29_add(r.c0, a.c0, b.c0);
         f29_add(r.c1, a.c1, b.c1);

@@ -25,9 +25,10 @@ struct FP29 {
 };
 
 DEV bool pair_odd() { return (__lane_id() & 1) != 0; }
-DEV uint32_t pair_swap(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
-}
+// quad_perm [1,0,3,2]. Every lane of the quad is read and (both lanes of a pair being active together)
+// every destination lane is written, so the move needs no defined previous value: mov_dpp leaves it
+// undefined and no zero is written to the destination in front of each move.
+DEV uint32_t pair_swap(uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true); }
 DEV F29 pair_swap(const F29& a) {
     F29 r;
 #pragma unroll
@@ -45,11 +46,6 @@ DEV F29 f29_select(bool c, const F29& a, const F29& b) {
     return r;
 }
 
-// b0 (the even lane's value) on both lanes of the pair: quad_perm [0,0,2,2]
-DEV uint32_t pair_even(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xA0, 0xF, 0xF, false); }
-// b1 (the odd lane's value) on both lanes: quad_perm [1,1,3,3]
-DEV uint32_t pair_odd_val(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xF5, 0xF, 0xF, false); }
-
 // 16p with every limb but the top raised by 2^29 (borrowed from the next limb): k_i - z_i is then
 // non-negative and < 2^30 for every normalized z < 8p, so 16p - z needs no borrow chain
 DEV constexpr uint32_t k16(int i) {
@@ -59,8 +55,10 @@ DEV constexpr uint32_t k16(int i) {
 // Two forms of the lane pair, identical in value and layout, differing only in how a product
 // prepares the partner's operand:
 //   FP29  (weighting and partial levels): y2 = 8p - b' by a borrow-chain subtraction;
-//   FP29A (the bucket accumulation, k_accum_aff): y1 and b1 come straight from DPP quad-permutes and
-//         y2 = 16p - b1 from the borrow-free k16 form (non-normalized limbs < 2^30). Columns stay below
+//   FP29A (the bucket accumulation, k_accum_aff): one pair_swap per operand value (b' = the partner's b),
+//         y1 = b0 and b1 by selects between b and b', and y2 = 16p - b1 from the borrow-free k16
+//         form (non-normalized limbs < 2^30; y1 and the odd lane's y2 = b1 stay normalized, so only
+//         one factor of one product per lane has 2^30 limbs). Columns stay below
 //         2^64: 14 products < 2^58 (a y1) + 14 < 2^59 (a' y2) + 14 m p < 2^58 = 56 x 2^58; the REDC
 //         input a0 b0 + a1 (16p - b1) < 192 p^2 < 2^406 p, so the result is < 2p as before.
 // FP29A is 3% faster in the accumulation (profiles/r02_ab9_xad.jsonl); in the weighting kernels,
@@ -72,18 +70,25 @@ struct FP29A {
 template <class P, bool kBorrowFree>
 struct PairOps {
     static constexpr bool kFusedSum = kBorrowFree;
+    // The second operand b of a borrow-free product, prepared from one exchange: with b' the partner's
+    // value, (y1, y2) = (b, k16 - b') on the even lane and (b', b) on the odd one, i.e. y1 = b0 on
+    // both, and y2 = 16p - b1 (limbs k_i - b1_i in [0, 2^30), see k16) on the even lane, b1 on the odd.
+    // The same words as the three quad-permutes per limb this replaces; a select costs one issue
+    // slot where a permute with its zeroed destination cost two.
+    static DEV void prep(F29& y1, F29& y2, const F29& b, bool odd) {
+        const F29 bp = pair_swap(b);
+#pragma unroll
+        for (int i = 0; i < 14; ++i) {
+            y1.v[i] = odd ? bp.v[i] : b.v[i];
+            y2.v[i] = odd ? b.v[i] : k16(i) - bp.v[i];
+        }
+    }
     static DEV void mul(P& r, const P& a, const P& b) {
         const bool odd = pair_odd();
         if constexpr (kBorrowFree) {
-            const uint32_t msk = odd ? 0u : 0xffffffffu;
-            F29 ap, y1, y2;
-#pragma unroll
-            for (int i = 0; i < 14; ++i) {
-                ap.v[i] = pair_swap(a.v.v[i]);
-                y1.v[i] = pair_even(b.v.v[i]);
-                const uint32_t z = pair_odd_val(b.v.v[i]);
-                y2.v[i] = (z ^ msk) + (msk & (k16(i) + 1u));  // even: k_i - z_i; odd: z_i
-            }
+            const F29 ap = pair_swap(a.v);
+            F29 y1, y2;
+            prep(y1, y2, b.v, odd);
             f29_mul2(r.v, a.v, y1, ap, y2);
         } else {
             const F29 ap = pair_swap(a.v), bp = pair_swap(b.v);
@@ -95,24 +100,51 @@ struct PairOps {
             f29_mul2(r.v, a.v, y1, ap, y2);
         }
     }
+    // r0 = a0 b0 and r1 = a1 b1, independent; the borrow-free form reduces them in lockstep
+    static DEV void mul_x2(P& r0, const P& a0, const P& b0, P& r1, const P& a1, const P& b1) {
+        if constexpr (kBorrowFree) {
+            const bool odd = pair_odd();
+            const F29 ap0 = pair_swap(a0.v), ap1 = pair_swap(a1.v);
+            F29 y1, y2, z1, z2;
+            prep(y1, y2, b0.v, odd);
+            prep(z1, z2, b1.v, odd);
+            f29_mul2_x2(r0.v, a0.v, y1, ap0, y2, r1.v, a1.v, z1, ap1, z2);
+        } else {
+            mul(r0, a0, b0);
+            mul(r1, a1, b1);
+        }
+    }
+    // r0 = a0^2 (a0.c1 < K0 p), r1 = a1^2 (a1.c1 < K1 p), independent
+    template <int K0, int K1>
+    static DEV void sqr_x2(P& r0, const P& a0, P& r1, const P& a1) {
+        if constexpr (kBorrowFree) {
+            const bool odd = pair_odd();
+            const F29 ap0 = pair_swap(a0.v), ap1 = pair_swap(a1.v);
+            F29 d0, d1, x0, y0, x1, y1;
+            f29_sub<K0>(d0, a0.v, ap0);
+            f29_sub<K1>(d1, a1.v, ap1);
+#pragma unroll
+            for (int i = 0; i < 14; ++i) {  // as sqr_b
+                x0.v[i] = odd ? ap0.v[i] : a0.v.v[i] + ap0.v[i];
+                y0.v[i] = odd ? a0.v.v[i] + a0.v.v[i] : d0.v[i];
+                x1.v[i] = odd ? ap1.v[i] : a1.v.v[i] + ap1.v[i];
+                y1.v[i] = odd ? a1.v.v[i] + a1.v.v[i] : d1.v[i];
+            }
+            f29_mul_x2(r0.v, x0, y0, r1.v, x1, y1);
+        } else {
+            sqr_b<K0>(r0, a0);
+            sqr_b<K1>(r1, a1);
+        }
+    }
     // r = a b + c d. Borrow-free form: one REDC of the lane's four products (f29_redc_sum4), < 2p;
     // otherwise two products and an addition, < 4p
     static DEV void mul_sum(P& r, const P& a, const P& b, const P& c, const P& d) {
         if constexpr (kBorrowFree) {
             const bool odd = pair_odd();
-            const uint32_t msk = odd ? 0u : 0xffffffffu;
-            F29 ap, y1, y2, cp, z1, z2;
-#pragma unroll
-            for (int i = 0; i < 14; ++i) {
-                ap.v[i] = pair_swap(a.v.v[i]);
-                y1.v[i] = pair_even(b.v.v[i]);
-                const uint32_t yb = pair_odd_val(b.v.v[i]);
-                y2.v[i] = (yb ^ msk) + (msk & (k16(i) + 1u));
-                cp.v[i] = pair_swap(c.v.v[i]);
-                z1.v[i] = pair_even(d.v.v[i]);
-                const uint32_t zd = pair_odd_val(d.v.v[i]);
-                z2.v[i] = (zd ^ msk) + (msk & (k16(i) + 1u));
-            }
+            const F29 ap = pair_swap(a.v), cp = pair_swap(c.v);
+            F29 y1, y2, z1, z2;
+            prep(y1, y2, b.v, odd);
+            prep(z1, z2, d.v, odd);
             // chains (a y1, ap y2) and (c z1, cp z2): one factor with 2^30 limbs (y2, z2) per chain, the
             // precondition of f29_redc_sum4
             f29_redc_sum4(r.v, a.v, y1, ap, y2, c.v, z1, cp, z2);

@@ -38,10 +38,15 @@ __device__ __forceinline__ void step(uint64_t& a, uint32_t x, uint32_t y) {
                      : "v"(x), "v"(y)
                      : "vcc");
         a = ((uint64_t)hi << 32) | lo;
-    } else {  // v_and_b32
+    } else if constexpr (OP == 4) {  // v_and_b32
         uint32_t lo = (uint32_t)a;
         asm volatile("v_and_b32 %0, %0, %1" : "+v"(lo) : "v"(x));
         a = (a & ~0xffffffffull) | lo;
+    } else if constexpr (OP == 5) {  // v_lshrrev_b64: the column's carry, acc >> 29
+        asm volatile("v_lshrrev_b64 %0, 29, %0" : "+v"(a));
+    } else {  // v_lshl_add_u64 with shift 0: the 64-bit join of a column sum and a carry
+        const uint64_t b = ((uint64_t)y << 32) | x;
+        asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(a) : "v"(b));
     }
 }
 
@@ -129,6 +134,10 @@ int main() {
     run<3, 2>("v_add_co+v_addc_co", buf, fclk);
     run<4, 1>("v_and_b32", buf, fclk);
     run<4, 2>("v_and_b32", buf, fclk);
+    run<5, 1>("v_lshrrev_b64", buf, fclk);
+    run<5, 2>("v_lshrrev_b64", buf, fclk);
+    run<6, 1>("v_lshl_add_u64", buf, fclk);
+    run<6, 2>("v_lshl_add_u64", buf, fclk);
     CHK(hipFree(buf));
     return 0;
 }
