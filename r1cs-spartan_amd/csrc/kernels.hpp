@@ -211,7 +211,8 @@ int sc_grid(uint64_t half);
 // polynomial at 0, 1, 2 (at 1 only if need1: otherwise result3[1] = 0 and the caller derives it from
 // the previous claim), and reduce over the blocks into result3 (3 Fr; device or host-mapped pinned
 // memory) - in the last block for small grids, by a second one-block launch otherwise.
-// partial: sc_grid(half) x 3 Fr of scratch; ticket: a device counter that is 0 (left 0).
+// partial: kRoundPartials Fr of scratch (3 per block; the quad / lane-pair and wave forms launch more
+// blocks than sc_grid(half)); ticket: a device counter that is 0 (left 0).
 void launch_sc1_round(bool fold, const Tables3& in, const Tables3& out, const Fr* Ein, Fr* Eout, const Fr& r,
                       uint64_t half, Fr* partial, uint32_t* ticket, Fr* result3, bool need1, hipStream_t s);
 void launch_sc2_round(bool fold, const Fr* Min, const Fr* Zin, Fr* Mout, Fr* Zout, const Fr& r, uint64_t half,

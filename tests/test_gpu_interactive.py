@@ -169,8 +169,10 @@ def test_interactive_claims_context_and_fourth_round_retry(spx, ctx, oc):
     p.close()
 
 
-@pytest.mark.parametrize("log_n", [1, 2, 6, 13])
+@pytest.mark.parametrize("log_n", [1, 2, 6, 13, 15, 16])
 def test_sumcheck_round_entry(spx, ctx, log_n):
+    """log_n 15 and 16 take the product build's wave-transposed kernels (2^14 pairs and more) with
+    P(1) asked for: round 1 fused (15) and through k_reduce_partials (16), the fold round fused (16)"""
     import spartan
 
     rs = random.Random(log_n)
