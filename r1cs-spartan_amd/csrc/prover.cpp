@@ -10,7 +10,7 @@
 // full (HBM-streaming) and weights 1/G of the buckets; each MSM exchanges one XYZZ point per rank.
 // Every rank replays the same transcript, so no challenge broadcast.
 #include "prover.hpp"
-#include "sc_message.hpp"
+#include "sumcheck_host.hpp"
 #include "pairing.hpp"
 
 #include <type_traits>
@@ -834,34 +834,11 @@ std::unique_ptr<Witness> witness_upload(Ctx& C, const uint8_t* v, size_t nv, con
 }
 
 // ====================================================================== prove helpers
-struct Ser {
-    std::vector<uint8_t> b;
-    void u64(uint64_t v) {
-        uint8_t t[8];
-        memcpy(t, &v, 8);
-        b.insert(b.end(), t, t + 8);
-    }
-    void fr(const HFr& x) {
-        uint8_t t[32];
-        host::fr_to_bytes(t, x);
-        b.insert(b.end(), t, t + 32);
-    }
-    void raw(const uint8_t* p, size_t k) { b.insert(b.end(), p, p + k); }
-};
-
-static HFr ld_hfr(const uint8_t* p) {  // device Montgomery bytes -> host Fr
-    HFr r;
-    memcpy(r.v, p, 32);
-    return r;
-}
+// (Ser, ld_hfr, eq1, quad_at and both sumchecks' host halves: sumcheck_host.hpp)
 static Fr dev_fr(const HFr& x) {  // host Fr -> device Fr (same Montgomery bytes), e.g. a kernel argument
     Fr r;
     memcpy(&r, x.v, 32);
     return r;
-}
-static HFr eq1(const HFr& tau, const HFr& t) {  // eq(tau, t) = 1 - tau - t + 2 tau t  (eq.rs:14)
-    HFr tt = tau * t;
-    return HFr::one() - tau - t + tt + tt;
 }
 
 size_t proof_size(int L) {
@@ -1225,15 +1202,105 @@ static void ser_open(Ser& s, const HFr& eval, const Affine<HFq2>& h, const std::
         s.raw(b, 96);
     }
 }
-
-// the quadratic through (0, g0), (1, g1), (2, g2) at t
-static HFr quad_at(const HFr g[3], const HFr& t) {
-    static const HFr inv2 = HFr::from_u64(2).inv();
-    const HFr one = HFr::one(), two = HFr::from_u64(2);
-    return g[0] * ((t - one) * (t - two) * inv2) - g[1] * (t * (t - two)) + g[2] * (t * (t - one) * inv2);
+// the public input v (lib.rs:65): absorbed as a Vec<Fr>, not a prover message
+static void absorb_public(Transcript& T, const std::vector<uint8_t>& v) {
+    Ser s;
+    s.u64(v.size() / 32);
+    s.raw(v.data(), v.size());
+    T.absorb(s.b.data(), s.b.size());
+}
+// the prover messages outside the sumchecks: the commitment (round 1), an opening (round 2)
+static void emit_commitment(ProofStream& io, int L, const Affine<HFq>& com) {
+    io.emit([&](Ser& s) {
+        s.u64((uint64_t)L);
+        uint8_t b[48];
+        host::g1_compress(b, com);
+        s.raw(b, 48);
+    });
+}
+static void emit_open(ProofStream& io, const HFr& eval, const Affine<HFq2>& h, const std::vector<Affine<HFq2>>& proofs) {
+    io.emit([&](Ser& s) { ser_open(s, eval, h, proofs); });
 }
 
 // ====================================================================== prove
+// A prove that throws may leave work queued that still reads W.z and writes the context's slots: drain
+// it while unwinding, so the caller may free the witness and the next proof on this context starts from
+// idle streams. all: the second stream too, and the MSM staging of both (prove(); the stubbed group and
+// the witness check queue on the main stream only and run no MSM).
+struct UnwindDrain {
+    Ctx& C;
+    bool all;
+    int pending = std::uncaught_exceptions();
+    ~UnwindDrain() {
+        if (std::uncaught_exceptions() <= pending) return;
+        (void)hipStreamSynchronize(C.stream);
+        if (!all) return;
+        if (C.side) (void)hipStreamSynchronize(C.side);
+        msm_ws_staging_reset(C.msm);
+        if (C.msm_side) msm_ws_staging_reset(C.msm_side);
+    }
+};
+
+// the index's SpMV Az, Bz, Cz of this rank's nl rows: the column-sorted entry list, or CSR rows
+static void launch_rows_spmv(Index& I, const Fr* z, Fr* Az, Fr* Bz, Fr* Cz, Fr* partial, uint64_t nl, hipStream_t s) {
+    if (I.rows_sliced.on)
+        launch_spmv_sliced(I.rows_sliced.view(), z, Az, Bz, Cz, I.rows_sliced.entries, s);
+    else
+        launch_sparse3(0, I.rows.view(), z, Az, Bz, Cz, nullptr, nl, I.rows.chunks.as<LongChunk>(), I.rows.nchunks,
+                       I.rows.lrows.as<LongRow>(), I.rows.nlrows, partial, s);
+}
+
+// A proof's device buffers, carved from the context's scratch (Fr units): one layout for prove() (this
+// rank's nl rows of one proof, with its challenges chdev behind) and for each proof of a lockstep group
+// (with the two buffers of its opening's fold chain behind; the group's challenges are one block).
+struct ProofScratch {
+    Fr *Az, *Bz, *Cz, *F1[3], *F2[3];  // SpMV outputs, their fold ping-pong
+    Fr *E1, *Ea, *Eb;                  // eq tables
+    Fr *M0, *M1, *M2, *Z1, *Z2;        // M_rx and z folds
+    Fr *partial, *eqlo, *eqhi, *eqf;   // partials, eq scratch
+    Fr* chdev = nullptr;               // tau, r_x, (r_a, r_b, r_c), ...
+    Fr *oA = nullptr, *oB = nullptr;
+    // carves from `base` (null: sizes only) and returns the Fr taken
+    uint64_t carve(Fr* base, const Index& I, uint64_t nl, int L, bool group) {
+        const uint64_t n2 = std::max<uint64_t>(nl / 2, 1), n4 = std::max<uint64_t>(nl / 4, 1);
+        uint64_t off = 0;
+        auto take = [&](uint64_t k) {
+            Fr* p = base ? base + off : nullptr;
+            off += k;
+            return p;
+        };
+        Az = take(nl), Bz = take(nl), Cz = take(nl);
+        for (int m = 0; m < 3; ++m) F1[m] = take(n2);
+        for (int m = 0; m < 3; ++m) F2[m] = take(n4);
+        E1 = take(n2), Ea = take(n4), Eb = take(std::max<uint64_t>(nl / 8, 1));
+        M0 = take(nl), M1 = take(n2), M2 = take(n4);
+        Z1 = take(n2), Z2 = take(n4);
+        partial = take(std::max<uint64_t>(kRoundPartials, std::max(I.rows.nchunks, I.cols.longc.nchunks)));
+        eqlo = take(8192), eqhi = take(8192), eqf = take(kEqScratch);
+        if (group)
+            oA = take(n2), oB = take(n4);
+        else
+            chdev = take(8 * L);
+        take(64);  // slack
+        return off;
+    }
+};
+
+// round 3's eq table of a 1-variable proof is the constant 1
+static void upload_one(Fr* E1, uint8_t* pin, hipStream_t s) {
+    const HFr one = HFr::one();
+    memcpy(pin, &one, 32);
+    SPX_HIP(hipMemcpyAsync(E1, pin, 32, hipMemcpyHostToDevice, s));
+}
+// a rank's three sums of a round -> the sums over all ranks
+static void sum_ranks(Comm& comm, HFr s[3]) {
+    if (comm.size() == 1) return;
+    const std::vector<HFr> all = allgather_fr(comm, {s[0], s[1], s[2]});
+    s[0] = s[1] = s[2] = HFr::zero();
+    for (size_t r = 0; r < all.size() / 3; ++r)
+        for (int k = 0; k < 3; ++k) s[k] += all[3 * r + k];
+}
+
 // ---------------------------------------------------------------- witness check
 // The kernel writes each proof's record straight into the context's pinned carve-out (as the sumcheck
 // rounds write their sums): it is read after the next wait that covers the launch, no copy is queued.
@@ -1290,20 +1357,7 @@ static WitnessReport witness_verdict(Ctx& C, int j, Comm& comm, uint64_t n) {
 std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts& o) {
     CtxClaim claim;
     if (!o.claimed) claim.take(C);  // before anything is queued: a refused prove touches nothing
-    // A prove that throws may leave work queued on both streams that still reads W.z and writes the
-    // context's slots: drain them while unwinding, so the caller may free the witness and the next
-    // proof on this context starts from idle streams.
-    struct UnwindDrain {
-        Ctx& C;
-        int pending = std::uncaught_exceptions();
-        ~UnwindDrain() {
-            if (std::uncaught_exceptions() <= pending) return;
-            (void)hipStreamSynchronize(C.stream);
-            if (C.side) (void)hipStreamSynchronize(C.side);
-            msm_ws_staging_reset(C.msm);
-            if (C.msm_side) msm_ws_staging_reset(C.msm_side);
-        }
-    } drain{C};
+    UnwindDrain drain{C, true};
     Timer tall;
     C.timings.clear();
     int phase = 0;
@@ -1338,49 +1392,21 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     const int log_v = ilog2(nvv);
     const Fr* z = W.z.as<Fr>();
     const Fr* zl = z + lo;
-    // scratch layout (Fr units)
-    const uint64_t n2 = std::max<uint64_t>(nl / 2, 1), n4 = std::max<uint64_t>(nl / 4, 1);
-    const uint64_t need = 3 * nl        // Az Bz Cz
-                          + 3 * n2 + 3 * n4  // fold ping-pong
-                          + n2 + n4 + std::max<uint64_t>(nl / 8, 1)  // E tables
-                          + nl + n2 + n4     // Mrx + fold
-                          + n2 + n4          // z fold
-                          + std::max<uint64_t>(kRoundPartials, std::max(I.rows.nchunks, I.cols.longc.nchunks))
-                          + 8192 * 2 + kEqScratch + 64 + 8 * L;  // partials, eq scratch, challenges
-    C.scratch.ensure(32 * need);
-    Fr* base = C.scratch.as<Fr>();
-    uint64_t cur_off = 0;
-    auto take = [&](uint64_t k) {
-        Fr* p = base + cur_off;
-        cur_off += k;
-        return p;
-    };
-    Fr *Az = take(nl), *Bz = take(nl), *Cz = take(nl);
-    Fr* F1[3] = {take(n2), take(n2), take(n2)};
-    Fr* F2[3] = {take(n4), take(n4), take(n4)};
-    Fr *E1 = take(n2), *Ea = take(n4), *Eb = take(std::max<uint64_t>(nl / 8, 1));
-    Fr *M0 = take(nl), *M1 = take(n2), *M2 = take(n4);
-    Fr *Z1 = take(n2), *Z2 = take(n4);
-    Fr* partial = take(std::max<uint64_t>(kRoundPartials, std::max(I.rows.nchunks, I.cols.longc.nchunks)));
-    Fr *eqlo = take(8192), *eqhi = take(8192), *eqf = take(kEqScratch);
-    Fr* chdev = take(8 * L);  // tau, r_x, (r_a, r_b, r_c), ...
+    ProofScratch S;
+    C.scratch.ensure(32 * S.carve(nullptr, I, nl, L, false));
+    S.carve(C.scratch.as<Fr>(), I, nl, L, false);
+    Fr* const partial = S.partial;
     uint8_t* hp = C.pin_at(Ctx::kPinHp, 1 << 16, 64 << 10);
 
     // ---- SpMV Az, Bz, Cz (challenge-independent: queued first, overlaps the commit's host work)
-    {
-        kp_begin(KP_SPMV, C.stream);
-        if (I.rows_sliced.on)
-            launch_spmv_sliced(I.rows_sliced.view(), z, Az, Bz, Cz, I.rows_sliced.entries, C.stream);
-        else
-            launch_sparse3(0, I.rows.view(), z, Az, Bz, Cz, nullptr, nl, I.rows.chunks.as<LongChunk>(), I.rows.nchunks,
-                           I.rows.lrows.as<LongRow>(), I.rows.nlrows, partial, C.stream);
-        kp_end(I.rows_bytes, C.stream);
-    }
+    kp_begin(KP_SPMV, C.stream);
+    launch_rows_spmv(I, z, S.Az, S.Bz, S.Cz, partial, nl, C.stream);
+    kp_end(I.rows_bytes, C.stream);
     // ---- witness check (off by default): one launch behind the SpMV; its record is read at the proof's
     // first host wait (witness_checked below), so it adds no wait
     const bool wcheck = C.witness_check();
     if (wcheck) {
-        const R1csCheckJob job = witness_job(C, 0, Az, Bz, Cz, partial);
+        const R1csCheckJob job = witness_job(C, 0, S.Az, S.Bz, S.Cz, partial);
         witness_check_launch(C, &job, 1, nl, lo);
     }
     auto witness_checked = [&] {
@@ -1406,13 +1432,7 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     // behind, one MSM pipeline less measured +2% index-cached at N = 1 (profiles/r06/r06zq_ab_lvl0_n1.jsonl)
     const bool lvl0_batch =
         C.lvl0_mode >= 0 ? C.lvl0_mode == 1 : (lvl0_batch_env || (G == 1 && o.cached && I.has_cache && !o.coins));
-    // SPX_CHECK_DERIVED=1 (tests): from round 2 on, a sumcheck round's value at 1 is derived from the
-    // previous claim on the host (P(0) + P(1) = claim); with this set the device computes it too and the
-    // prove fails with SPX_SUMCHECK if they differ (the identity pinned round by round, every rank count)
-    const bool check_derived = [] {
-        const char* e = getenv("SPX_CHECK_DERIVED");
-        return e && e[0] == '1';
-    }();
+    const bool check = check_derived();
     if (G > 1 && !C.knobs_agreed) {
         // the level-0 mode decides the order and sizes of a proof's exchanges: every rank of the
         // communicator must read the same SPX_LVL0 (one exchange on a context's first sharded proof)
@@ -1438,7 +1458,8 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     if (!o.stub) commit_launch(C, *P, z, n, sh);
     if (early0) lvl0_launch(C, *P, z, L, sh);
     if (side0) lvl0_launch(C, *P, z, L, sh, true);
-    Transcript T(o.mode == 1, o.seed, o.coins);
+    ProofStream io{Transcript(o.mode == 1, o.seed, o.coins), {}};
+    Transcript& T = io.T;
     const uint64_t ctr = C.prove_seq++;
     const uint64_t seq = o.seq >= 0 ? (uint64_t)o.seq : ctr;
     const Blake2s* absorbed = o.await_absorbed ? o.await_absorbed() : o.absorbed;
@@ -1460,12 +1481,7 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
         memcpy(&h, all.data() + sizeof(Blake2s) * owner, sizeof(Blake2s));
         T.set_state(h);
     }
-    {
-        Ser s;
-        s.u64(nvv);
-        s.raw(W.v.data(), W.v.size());
-        T.absorb(s.b.data(), s.b.size());
-    }
+    absorb_public(T, W.v);
     mark("transcript_matrices", tp);
     Affine<HFq> com = o.stub ? Affine<HFq>{HFq::zero(), HFq::zero(), true} : commit_finish(C, *P, z, n, comm);
     // the commitment's wait covered the check: before any challenge is drawn or message emitted (a
@@ -1473,15 +1489,7 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     if (wcheck && !o.stub) witness_checked();
     Affine<HFq2> proof0{};
     if (early0) proof0 = lvl0_finish(C, *P, z, L, comm);
-    Ser proof;
-    {
-        size_t m0 = proof.b.size();
-        proof.u64((uint64_t)L);
-        uint8_t b[48];
-        host::g1_compress(b, com);
-        proof.raw(b, 48);
-        T.feed(proof.b.data() + m0, proof.b.size() - m0);
-    }
+    emit_commitment(io, L, com);
     mark("commit", tp);
     // ---- round 2: open at (r_v, 0...0) (prover.rs:143-160)
     std::vector<HFr> pt1(L, HFr::zero());
@@ -1492,38 +1500,26 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
         if (wcheck && o.stub) witness_checked();  // the stubbed proof's first wait (r_v is derived, nothing emitted)
         if (side0) op.proofs[0] = proof0 = lvl0_finish(C, *P, z, L, comm, true);
         if (share0 && !early0 && !side0) proof0 = op.proofs[0];
-        size_t m0 = proof.b.size();
-        ser_open(proof, op.eval, h_of(P), op.proofs);
-        T.feed(proof.b.data() + m0, proof.b.size() - m0);
+        emit_open(io, op.eval, h_of(P), op.proofs);
     }
     mark("open_rv", tp);
     // ---- round 3: tau, eq, sumcheck #1 setup (prover.rs:163-196)
     std::vector<HFr> tau(L);
     for (int i = 0; i < L; ++i) tau[i] = T.rand_fr();
     memcpy(hp, tau.data(), 32 * L);
-    SPX_HIP(hipMemcpyAsync(chdev, hp, 32 * L, hipMemcpyHostToDevice, C.stream));
+    SPX_HIP(hipMemcpyAsync(S.chdev, hp, 32 * L, hipMemcpyHostToDevice, C.stream));
     // E_1[b] = eq(tau_1..tau_{L-1}, b) on this rank's block of b
     if (L >= 2)
-        launch_eq_table(chdev + 1, L - 1, (uint64_t)rank * (nl / 2), nl / 2, E1, eqlo, eqhi, C.stream);
-    else {
-        const HFr one = HFr::one();
-        memcpy(hp + 4096, &one, 32);
-        SPX_HIP(hipMemcpyAsync(E1, hp + 4096, 32, hipMemcpyHostToDevice, C.stream));
-    }
-    {
-        size_t m0 = proof.b.size();
-        proof.u64((uint64_t)(L + 2));  // IndexInfo.max_multiplicands (reconstructed field order)
-        proof.u64((uint64_t)L);        // IndexInfo.num_variables
-        T.feed(proof.b.data() + m0, proof.b.size() - m0);
-    }
+        launch_eq_table(S.chdev + 1, L - 1, (uint64_t)rank * (nl / 2), nl / 2, S.E1, S.eqlo, S.eqhi, C.stream);
+    else
+        upload_one(S.E1, hp + 4096, C.stream);
     // ---- sumcheck #1 (lib.rs:86-103)
-    proof.u64((uint64_t)L);
-    std::vector<HFr> r_x;
-    HFr Cc = HFr::one(), claim1 = HFr::zero();
+    io.sumcheck_header(L + 2, L);
+    Sumcheck1 s1(io, std::move(tau));
     Fr* res_dev = C.pin_dev<Fr>(hp);  // the rounds' sums land in pinned host memory (hp)
-    Tables3 cur{{Az, Bz, Cz}};
-    const Fr* Ecur = E1;
-    Fr* Ebuf[2] = {Ea, Eb};
+    Tables3 cur{{S.Az, S.Bz, S.Cz}};
+    const Fr* Ecur = S.E1;
+    Fr* Ebuf[2] = {S.Ea, S.Eb};
     // The last ht1 rounds of each sumcheck run on the host, as in prove_group: each rank binds its local
     // tables (<= 64 entries) and, sharded, the ranks' tables are gathered in rank order (the g high
     // variables) before the last g + ht1 rounds. Unsharded: one proof at a time 22.5 vs 22.6 ms
@@ -1538,168 +1534,63 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
         Tables3 out{{nullptr, nullptr, nullptr}};
         Fr* Eout = nullptr;
         if (fold) {
-            Fr** fb = (i % 2 == 0) ? F1 : F2;
+            Fr** fb = (i % 2 == 0) ? S.F1 : S.F2;
             out = Tables3{{fb[0], fb[1], fb[2]}};
             if (i < L - g) Eout = Ebuf[i & 1];
         }
-        // from round 2 on, P_i(0) + P_i(1) = P_{i-1}(r_{i-1}) (the claim) is an identity of the folded
-        // tables, so G(1) follows from G(0): Cc (1 - tau) G(0) + Cc tau G(1) = claim; the kernel skips it
-        // (2 of its 12 Fr products per pair). Exact field arithmetic: the same message bytes.
-        const HFr ct = Cc * tau[i - 1];
-        const bool derive1 = fold && !ct.is_zero();
-        launch_sc1_round(fold, cur, out, Ecur, Eout, fold ? dev_fr(r_x[i - 2]) : Fr{}, half, partial, C.ticket, res_dev,
-                         !derive1 || check_derived, C.stream);
+        launch_sc1_round(fold, cur, out, Ecur, Eout, fold ? dev_fr(s1.r[i - 2]) : Fr{}, half, partial, C.ticket, res_dev,
+                         !s1.derivable() || check, C.stream);
         C.sync();
         HFr gs[3] = {ld_hfr(hp), ld_hfr(hp + 32), ld_hfr(hp + 64)};
-        if (G > 1) {
-            std::vector<HFr> all = allgather_fr(comm, {gs[0], gs[1], gs[2]});
-            gs[0] = gs[1] = gs[2] = HFr::zero();
-            for (int r = 0; r < G; ++r)
-                for (int k = 0; k < 3; ++k) gs[k] += all[3 * r + k];
-        }
-        if (derive1) {
-            const HFr d1 = (claim1 - (Cc - ct) * gs[0]) * ct.inv();
-            if (check_derived && !(d1 == gs[1]))
-                throw SpxError(kSumcheck, "sumcheck 1 round " + std::to_string(i) + ": derived G(1) differs from the device's");
-            gs[1] = d1;
-        }
-        std::vector<HFr> msg = sc1_message(Cc, tau[i - 1], gs, L);
-        size_t m0 = proof.b.size();
-        proof.u64(msg.size());
-        for (auto& e : msg) proof.fr(e);
-        T.feed(proof.b.data() + m0, proof.b.size() - m0);
-        HFr ch = T.rand_fr();
-        r_x.push_back(ch);
-        const HFr eqc = eq1(tau[i - 1], ch);
-        claim1 = Cc * eqc * quad_at(gs, ch);  // P_i(r_i)
-        Cc = Cc * eqc;
+        sum_ranks(comm, gs);
+        s1.device_round(gs, check);
         if (fold) {
             cur = out;
             if (Eout) Ecur = Eout;
         }
     }
-    // local tables now hold tn entries each (2 when sharded; folded up to r_{L-g-ht1-1}); bind r_{L-g-ht1}
-    // on the host
-    HFr va, vb, vc;
-    {
-        for (int m = 0; m < 3; ++m)
-            SPX_HIP(hipMemcpyAsync(hp + 32 * tn * m, cur.t[m], 32 * tn, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        const HFr r = r_x.back();
-        // this rank's tables bound at r: 3 x tn / 2 entries; gathered in rank order (rank = the high
-        // variables), the remaining g + ht1 variables' tables
-        const uint32_t hn = tn / 2;
-        std::vector<HFr> mine(3 * hn);
-        for (int m = 0; m < 3; ++m)
-            for (uint32_t b = 0; b < hn; ++b) {
-                const HFr a0 = ld_hfr(hp + 32 * (tn * m + 2 * b)), a1 = ld_hfr(hp + 32 * (tn * m + 2 * b + 1));
-                mine[m * hn + b] = a0 + r * (a1 - a0);
-            }
-        std::vector<HFr> tabs[3];
-        const std::vector<HFr> all = G == 1 ? mine : allgather_fr(comm, mine);
-        for (int m = 0; m < 3; ++m)
-            for (int r2 = 0; r2 < G; ++r2)
-                for (uint32_t b = 0; b < hn; ++b) tabs[m].push_back(all[(size_t)3 * hn * r2 + m * hn + b]);
-        // last g (+ ht1) rounds on the gathered tables (size 2^g, or 2^ht1 unsharded), same message formula
-        for (int i = L - g - ht1 + 1; i <= L; ++i) {
-            const size_t half = tabs[0].size() / 2;
-            const int c = i - 1;
-            HFr gs[3] = {HFr::zero(), HFr::zero(), HFr::zero()};
-            for (size_t b = 0; b < half; ++b) {
-                HFr e = HFr::one();  // eq(tau_{c+1..L-1}, b)
-                for (int j = c + 1; j < L; ++j) e *= ((b >> (j - c - 1)) & 1) ? tau[j] : HFr::one() - tau[j];
-                HFr x0[3], x1[3], y[3];
-                for (int m = 0; m < 3; ++m) {
-                    x0[m] = tabs[m][2 * b];
-                    x1[m] = tabs[m][2 * b + 1];
-                    y[m] = x1[m] + x1[m] - x0[m];
-                }
-                gs[0] += (x0[0] * x0[1] - x0[2]) * e;
-                gs[1] += (x1[0] * x1[1] - x1[2]) * e;
-                gs[2] += (y[0] * y[1] - y[2]) * e;
-            }
-            std::vector<HFr> msg = sc1_message(Cc, tau[c], gs, L);
-            size_t m0 = proof.b.size();
-            proof.u64(msg.size());
-            for (auto& e : msg) proof.fr(e);
-            T.feed(proof.b.data() + m0, proof.b.size() - m0);
-            HFr ch = T.rand_fr();
-            r_x.push_back(ch);
-            Cc = Cc * eq1(tau[c], ch);
-            for (int m = 0; m < 3; ++m) {
-                std::vector<HFr> nt(half);
-                for (size_t b = 0; b < half; ++b) nt[b] = tabs[m][2 * b] + ch * (tabs[m][2 * b + 1] - tabs[m][2 * b]);
-                tabs[m].swap(nt);
-            }
-        }
-        va = tabs[0][0];
-        vb = tabs[1][0];
-        vc = tabs[2][0];
-    }
+    // local tables now hold tn entries each (2 when sharded; folded up to r_{L-g-ht1-1}): r_{L-g-ht1} is
+    // bound on the host, the ranks' tables are gathered, and the last g + ht1 rounds run there
+    for (int m = 0; m < 3; ++m)
+        SPX_HIP(hipMemcpyAsync(hp + 32 * tn * m, cur.t[m], 32 * tn, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    std::vector<HFr> mine = s1.bind(hp, tn);
+    const std::vector<HFr> vabc = s1.tail(rank_order(G == 1 ? std::move(mine) : allgather_fr(comm, mine), 3, G));
     mark("sumcheck1", tp);
     // ---- round 4 (prover.rs:210-228)
-    {
-        size_t m0 = proof.b.size();
-        proof.fr(va);
-        proof.fr(vb);
-        proof.fr(vc);
-        T.feed(proof.b.data() + m0, proof.b.size() - m0);
-    }
+    io.emit([&](Ser& s) {
+        for (int m = 0; m < 3; ++m) s.fr(vabc[m]);
+    });
     HFr rabc[3] = {T.rand_fr(), T.rand_fr(), T.rand_fr()};
     // ---- round 5: M_rx = sum_m r_m M(r_x, .) on this rank's columns (prover.rs:230-255)
-    Fr* rxdev = chdev + 2 * L;  // r_x (L) then r_abc (3)
-    memcpy(hp, r_x.data(), 32 * L);
+    Fr* rxdev = S.chdev + 2 * L;  // r_x (L) then r_abc (3)
+    memcpy(hp, s1.r.data(), 32 * L);
     memcpy(hp + 32 * L, rabc, 96);
     SPX_HIP(hipMemcpyAsync(rxdev, hp, 32 * (L + 3), hipMemcpyHostToDevice, C.stream));
     {
         kp_begin(KP_MTV, C.stream);
-        I.cols.launch(rxdev, L, rxdev + L, M0, eqf, partial, C.stream);
+        I.cols.launch(rxdev, L, rxdev + L, S.M0, S.eqf, partial, C.stream);
         kp_end(I.cols_bytes, C.stream);
     }
-    {
-        size_t m0 = proof.b.size();
-        proof.u64(2);
-        proof.u64((uint64_t)L);
-        T.feed(proof.b.data() + m0, proof.b.size() - m0);
-    }
+    io.sumcheck_header(2, L);
     mark("eval_on_x", tp);
     // ---- sumcheck #2 (lib.rs:114-131)
-    proof.u64((uint64_t)L);
-    std::vector<HFr> r_y;
-    HFr claim2 = HFr::zero();
-    const Fr* Mc = M0;
+    Sumcheck2 s2(io, L);
+    const Fr* Mc = S.M0;
     const Fr* Zc = zl;
-    Fr* Mb[2] = {M1, M2};
-    Fr* Zb[2] = {Z1, Z2};
+    Fr* Mb[2] = {S.M1, S.M2};
+    Fr* Zb[2] = {S.Z1, S.Z2};
     for (int i = 1; i <= L - g - ht1; ++i) {
         const uint64_t half = nl >> i;
         const bool fold = i >= 2;
         Fr* Mo = fold ? Mb[i & 1] : nullptr;
         Fr* Zo = fold ? Zb[i & 1] : nullptr;
-        // from round 2 on, P(1) = claim - P(0) (the folded tables' identity): the kernel skips it
-        launch_sc2_round(fold, Mc, Zc, Mo, Zo, fold ? dev_fr(r_y[i - 2]) : Fr{}, half, partial, C.ticket, res_dev,
-                         !fold || check_derived, C.stream);
+        launch_sc2_round(fold, Mc, Zc, Mo, Zo, fold ? dev_fr(s2.r[i - 2]) : Fr{}, half, partial, C.ticket, res_dev,
+                         !s2.derivable() || check, C.stream);
         C.sync();
         HFr ps[3] = {ld_hfr(hp), ld_hfr(hp + 32), ld_hfr(hp + 64)};
-        if (G > 1) {
-            std::vector<HFr> all = allgather_fr(comm, {ps[0], ps[1], ps[2]});
-            ps[0] = ps[1] = ps[2] = HFr::zero();
-            for (int r = 0; r < G; ++r)
-                for (int k = 0; k < 3; ++k) ps[k] += all[3 * r + k];
-        }
-        if (fold) {
-            const HFr d1 = claim2 - ps[0];
-            if (check_derived && !(d1 == ps[1]))
-                throw SpxError(kSumcheck, "sumcheck 2 round " + std::to_string(i) + ": derived P(1) differs from the device's");
-            ps[1] = d1;
-        }
-        size_t m0 = proof.b.size();
-        proof.u64(3);
-        for (int k = 0; k < 3; ++k) proof.fr(ps[k]);
-        T.feed(proof.b.data() + m0, proof.b.size() - m0);
-        HFr ch = T.rand_fr();
-        r_y.push_back(ch);
-        claim2 = quad_at(ps, ch);  // P_i(r_i)
+        sum_ranks(comm, ps);
+        s2.device_round(ps, check);
         if (fold) {
             Mc = Mo;
             Zc = Zo;
@@ -1709,55 +1600,18 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
         SPX_HIP(hipMemcpyAsync(hp, Mc, 32 * tn, hipMemcpyDeviceToHost, C.stream));
         SPX_HIP(hipMemcpyAsync(hp + 32 * tn, Zc, 32 * tn, hipMemcpyDeviceToHost, C.stream));
         C.sync();
-        const HFr r = r_y.back();
-        const uint32_t hn = tn / 2;
-        std::vector<HFr> mine(2 * hn);
-        for (uint32_t b = 0; b < hn; ++b) {
-            const HFr m0v = ld_hfr(hp + 32 * (2 * b)), m1v = ld_hfr(hp + 32 * (2 * b + 1));
-            const HFr z0 = ld_hfr(hp + 32 * (tn + 2 * b)), z1 = ld_hfr(hp + 32 * (tn + 2 * b + 1));
-            mine[b] = m0v + r * (m1v - m0v);
-            mine[hn + b] = z0 + r * (z1 - z0);
-        }
-        const std::vector<HFr> all = G == 1 ? mine : allgather_fr(comm, mine);
-        std::vector<HFr> Mt, Zt;
-        for (int r2 = 0; r2 < G; ++r2)
-            for (uint32_t b = 0; b < hn; ++b) {
-                Mt.push_back(all[(size_t)2 * hn * r2 + b]);
-                Zt.push_back(all[(size_t)2 * hn * r2 + hn + b]);
-            }
-        for (int i = L - g - ht1 + 1; i <= L; ++i) {
-            const size_t half = Mt.size() / 2;
-            HFr ps[3] = {HFr::zero(), HFr::zero(), HFr::zero()};
-            for (size_t b = 0; b < half; ++b) {
-                HFr m0v = Mt[2 * b], m1v = Mt[2 * b + 1], z0 = Zt[2 * b], z1 = Zt[2 * b + 1];
-                ps[0] += m0v * z0;
-                ps[1] += m1v * z1;
-                ps[2] += (m1v + m1v - m0v) * (z1 + z1 - z0);
-            }
-            size_t m0 = proof.b.size();
-            proof.u64(3);
-            for (int k = 0; k < 3; ++k) proof.fr(ps[k]);
-            T.feed(proof.b.data() + m0, proof.b.size() - m0);
-            HFr ch = T.rand_fr();
-            r_y.push_back(ch);
-            std::vector<HFr> nm(half), nz(half);
-            for (size_t b = 0; b < half; ++b) {
-                nm[b] = Mt[2 * b] + ch * (Mt[2 * b + 1] - Mt[2 * b]);
-                nz[b] = Zt[2 * b] + ch * (Zt[2 * b + 1] - Zt[2 * b]);
-            }
-            Mt.swap(nm);
-            Zt.swap(nz);
-        }
+        mine = s2.bind(hp, tn);
+        s2.tail(rank_order(G == 1 ? std::move(mine) : allgather_fr(comm, mine), 2, G));
     }
     mark("sumcheck2", tp);
     // ---- round 6: open at r_y (prover.rs:268-281)
     {
-        OpenOut op = o.stub ? open_stub(C, zl, L, r_y, G) : open_z(C, *P, z, L, r_y, comm, share0 ? &proof0 : nullptr);
-        ser_open(proof, op.eval, h_of(P), op.proofs);
+        OpenOut op = o.stub ? open_stub(C, zl, L, s2.r, G) : open_z(C, *P, z, L, s2.r, comm, share0 ? &proof0 : nullptr);
+        ser_open(io.proof, op.eval, h_of(P), op.proofs);
     }
     mark("open_ry", tp);
     C.timings.emplace_back("total", tall.us());
-    return proof.b;
+    return std::move(io.proof.b);
 }
 
 // ====================================================================== lockstep groups
@@ -1767,21 +1621,15 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
 // profiles/r05/r05zg_c2_busy.txt), each proof waiting its turn in a queue. Here the k proofs' sumcheck
 // rounds are one launch each (launch_sc1_round_group: blockIdx.y = proof) with one wait, and the other
 // steps queue the k proofs' launches back to back before one wait. Every value is computed by the same
-// kernels and host formulas as prove(), so each proof's bytes are its own prove()'s.
+// kernels as prove() and by the same host code (sumcheck_host.hpp), so each proof's bytes are its own
+// prove()'s.
 std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* Ws, int k, const ProveOpts* os,
                                               std::vector<std::string>* rejected) {
     static_assert(kGroupMax <= 16, "one sumcheck ticket per proof of a group: Ctx::ticket holds 16 counters");
     if (k < 1 || k > kGroupMax) invalid("lockstep group size must be 1.." + std::to_string(kGroupMax));
     CtxClaim claim;
     claim.take(C);
-    struct UnwindDrain {
-        Ctx& C;
-        int pending = std::uncaught_exceptions();
-        ~UnwindDrain() {
-            if (std::uncaught_exceptions() <= pending) return;
-            (void)hipStreamSynchronize(C.stream);
-        }
-    } drain{C};
+    UnwindDrain drain{C, false};
     // a group records no per-phase marks (its phases interleave k proofs): spx_last_timings reports
     // its total alone, and the host-phase counters (spx_host_phase_stats) count prove() calls only
     C.timings.clear();
@@ -1796,16 +1644,10 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         if (!is_pow2(Ws[j]->v.size() / 32)) invalid("public input should be power of two");
         if (Ws[j]->n != n) invalid("|v| + |w| != number of variables");  // prover.rs:117-119
     }
-    const bool check_derived = [] {
-        const char* e = getenv("SPX_CHECK_DERIVED");
-        return e && e[0] == '1';
-    }();
-    // per-proof scratch, prove()'s layout at G = 1
-    const uint64_t n2 = std::max<uint64_t>(nl / 2, 1), n4 = std::max<uint64_t>(nl / 4, 1);
-    const uint64_t npart = std::max<uint64_t>(kRoundPartials, std::max(I.rows.nchunks, I.cols.longc.nchunks));
-    // (plus the opening folds' two buffers per proof: the group's fold chains run side by side)
-    const uint64_t need = 3 * nl + 3 * n2 + 3 * n4 + n2 + n4 + std::max<uint64_t>(nl / 8, 1) + nl + n2 + n4 + n2 + n4 +
-                          npart + 8192 * 2 + kEqScratch + 64 + n2 + n4;
+    const bool check = check_derived();
+    // per-proof scratch, prove()'s layout at G = 1 (plus the opening folds' two buffers per proof: the
+    // group's fold chains run side by side)
+    const uint64_t need = ProofScratch().carve(nullptr, I, nl, L, true);
     // the group's challenges: proof j's tau, r_x, r_abc at chg + 8 L j (one host-to-device copy each time)
     C.scratch.ensure(32 * (need + 8 * (uint64_t)L) * (uint64_t)k);
     Fr* chg = C.scratch.as<Fr>() + need * k;
@@ -1814,49 +1656,29 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
     uint8_t* hp0 = C.pin_at(Ctx::kPinHp, kGroupMax * 8192, 128 << 10);
     uint8_t* ho0 = C.pin_at(Ctx::kPinOpen, kGroupMax * 2048, 56 << 10);
     uint8_t* stage = C.pin_at(Ctx::kPinStage, (size_t)32 * 8 * L * k, 128 << 10);
-    struct P {
-        Fr *Az, *Bz, *Cz, *F1[3], *F2[3], *E1, *Ea, *Eb, *M0, *M1, *M2, *Z1, *Z2, *partial, *eqlo, *eqhi, *eqf, *chdev;
-        Fr *oA, *oB;
+    struct P : ProofScratch {
         uint8_t *hp, *ho;
         Fr* res_dev;
         const Fr* z;
         int log_v;
-        Transcript T;
-        Ser proof;
-        std::vector<HFr> tau, r_x, r_y;
-        HFr Cc, claim1, claim2;
+        ProofStream io;
+        Sumcheck1 s1;
+        Sumcheck2 s2;
         Tables3 cur;
         const Fr* Ecur;
         const Fr *Mc, *Zc;
     };
-    std::vector<P> ps;
-    ps.reserve(k);
+    std::vector<P> ps(k);  // (sized once: s1 and s2 point at their proof's io)
     for (int j = 0; j < k; ++j) {
-        Fr* base = C.scratch.as<Fr>() + need * j;
-        uint64_t off = 0;
-        auto take = [&](uint64_t c) {
-            Fr* q = base + off;
-            off += c;
-            return q;
-        };
-        P p;
-        p.Az = take(nl), p.Bz = take(nl), p.Cz = take(nl);
-        for (int m = 0; m < 3; ++m) p.F1[m] = take(n2);
-        for (int m = 0; m < 3; ++m) p.F2[m] = take(n4);
-        p.E1 = take(n2), p.Ea = take(n4), p.Eb = take(std::max<uint64_t>(nl / 8, 1));
-        p.M0 = take(nl), p.M1 = take(n2), p.M2 = take(n4);
-        p.Z1 = take(n2), p.Z2 = take(n4);
-        p.partial = take(npart);
-        p.eqlo = take(8192), p.eqhi = take(8192), p.eqf = take(kEqScratch);
-        p.oA = take(n2), p.oB = take(n4);
+        P& p = ps[j];
+        p.carve(C.scratch.as<Fr>() + need * j, I, nl, L, true);
         p.chdev = chg + (uint64_t)8 * L * j;
         p.hp = hp0 + 8192 * j;
         p.ho = ho0 + 2048 * j;
         p.res_dev = C.pin_dev<Fr>(p.hp);
         p.z = Ws[j]->z.as<Fr>();
         p.log_v = ilog2(Ws[j]->v.size() / 32);
-        p.T = Transcript(os[j].mode == 1, os[j].seed, nullptr);
-        ps.push_back(std::move(p));
+        p.io.T = Transcript(os[j].mode == 1, os[j].seed, nullptr);
     }
     // per-proof pointer arrays for the group launchers
     auto each = [&](auto f) {
@@ -1874,9 +1696,7 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         // one index stream for the group (k_spmv_sliced_group), z and the outputs per proof
         kp_end(I.rows_index_bytes + (I.rows_bytes - I.rows_index_bytes) * k, C.stream);
     } else {
-        for (auto& p : ps)
-            launch_sparse3(0, I.rows.view(), p.z, p.Az, p.Bz, p.Cz, nullptr, nl, I.rows.chunks.as<LongChunk>(),
-                           I.rows.nchunks, I.rows.lrows.as<LongRow>(), I.rows.nlrows, p.partial, C.stream);
+        for (auto& p : ps) launch_rows_spmv(I, p.z, p.Az, p.Bz, p.Cz, p.partial, nl, C.stream);
     }
     // ---- witness check (off by default): the k proofs' checks in one launch (blockIdx.y = proof); the
     // records are read behind the group's first wait (round 2's)
@@ -1893,21 +1713,13 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         const ProveOpts& o = os[j];
         C.prove_seq++;
         if (o.cached && I.has_cache)
-            p.T.set_state(I.cache);
+            p.io.T.set_state(I.cache);
         else {
             const Blake2s* absorbed = o.await_absorbed ? o.await_absorbed() : o.absorbed;
-            p.T.set_state(absorbed ? *absorbed : absorb_matrices(I));
+            p.io.T.set_state(absorbed ? *absorbed : absorb_matrices(I));
         }
-        Ser s;
-        s.u64(Ws[j]->v.size() / 32);
-        s.raw(Ws[j]->v.data(), Ws[j]->v.size());
-        p.T.absorb(s.b.data(), s.b.size());
-        const Affine<HFq> com{HFq::zero(), HFq::zero(), true};
-        p.proof.u64((uint64_t)L);
-        uint8_t b[48];
-        host::g1_compress(b, com);
-        p.proof.raw(b, 48);
-        p.T.feed(p.proof.b.data(), p.proof.b.size());
+        absorb_public(p.io.T, Ws[j]->v);
+        emit_commitment(p.io, L, Affine<HFq>{HFq::zero(), HFq::zero(), true});
     }
     // stubbed openings: every proof's z(point) by open_stub's fold chain, one launch per step for the
     // group, the values written straight into pinned memory; one wait
@@ -1922,18 +1734,13 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         launch_open_eval_group(k, zs.data(), as.data(), bs.data(), flat.data(), L, nl, last.data(), C.stream);
         C.sync();
         const std::vector<Affine<HFq2>> none(L, Affine<HFq2>{HFq2::zero(), HFq2::zero(), true});
-        for (int j = 0; j < k; ++j) {
-            P& p = ps[j];
-            const size_t m0 = p.proof.b.size();
-            ser_open(p.proof, ld_hfr(p.ho), h_of(nullptr), none);
-            p.T.feed(p.proof.b.data() + m0, p.proof.b.size() - m0);
-        }
+        for (auto& p : ps) emit_open(p.io, ld_hfr(p.ho), h_of(nullptr), none);
     };
     {  // round 2: open at (r_v, 0...0)
         std::vector<std::vector<HFr>> pts(k);
         for (int j = 0; j < k; ++j) {
             pts[j].assign(L, HFr::zero());
-            for (int i = 0; i < ps[j].log_v; ++i) pts[j][i] = ps[j].T.rand_fr();
+            for (int i = 0; i < ps[j].log_v; ++i) pts[j][i] = ps[j].io.T.rand_fr();
         }
         open_all(pts);
     }
@@ -1947,9 +1754,10 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
     // ---- round 3: tau (one copy for the group), eq tables (one launch pair); sumcheck 1 setup
     for (int j = 0; j < k; ++j) {
         P& p = ps[j];
-        p.tau.resize(L);
-        for (int i = 0; i < L; ++i) p.tau[i] = p.T.rand_fr();
-        memcpy(stage + (size_t)32 * 8 * L * j, p.tau.data(), 32 * L);
+        std::vector<HFr> tau(L);
+        for (int i = 0; i < L; ++i) tau[i] = p.io.T.rand_fr();
+        memcpy(stage + (size_t)32 * 8 * L * j, tau.data(), 32 * L);
+        p.s1 = Sumcheck1(p.io, std::move(tau));
     }
     SPX_HIP(hipMemcpyAsync(chg, stage, (size_t)32 * 8 * L * k, hipMemcpyHostToDevice, C.stream));
     if (L >= 2) {
@@ -1960,18 +1768,8 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         launch_eq_table_group(k, rs.data(), L - 1, 0, nl / 2, outs.data(), lo.data(), hi.data(), C.stream);
     }
     for (auto& p : ps) {
-        if (L < 2) {
-            const HFr one = HFr::one();
-            memcpy(p.hp + 4096, &one, 32);
-            SPX_HIP(hipMemcpyAsync(p.E1, p.hp + 4096, 32, hipMemcpyHostToDevice, C.stream));
-        }
-        const size_t m0 = p.proof.b.size();
-        p.proof.u64((uint64_t)(L + 2));
-        p.proof.u64((uint64_t)L);
-        p.T.feed(p.proof.b.data() + m0, p.proof.b.size() - m0);
-        p.proof.u64((uint64_t)L);
-        p.Cc = HFr::one();
-        p.claim1 = HFr::zero();
+        if (L < 2) upload_one(p.E1, p.hp + 4096, C.stream);
+        p.io.sumcheck_header(L + 2, L);
         p.cur = Tables3{{p.Az, p.Bz, p.Cz}};
         p.Ecur = p.E1;
     }
@@ -1984,11 +1782,10 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
     const int ht = std::min(kGroupHostTail, L - 1);
     // ---- sumcheck 1: one launch and one wait per round for the group
     std::vector<Sc1Job> j1(k);
-    std::vector<char> derive(k);
     for (int i = 1; i <= L - ht; ++i) {
         const uint64_t half = nl >> i;
         const bool fold = i >= 2;
-        bool need1 = check_derived;
+        bool need1 = check;
         for (int j = 0; j < k; ++j) {
             P& p = ps[j];
             Sc1Job& jb = j1[j];
@@ -2001,36 +1798,18 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
                 jb.out = Tables3{{fb[0], fb[1], fb[2]}};
                 if (i < L) jb.Eout = (i & 1) ? p.Eb : p.Ea;
             }
-            jb.r = fold ? dev_fr(p.r_x[i - 2]) : Fr{};
+            jb.r = fold ? dev_fr(p.s1.r[i - 2]) : Fr{};
             jb.partial = p.partial;
             jb.ticket = C.ticket + j;
             jb.result3 = p.res_dev;
-            const HFr ct = p.Cc * p.tau[i - 1];
-            derive[j] = fold && !ct.is_zero();
-            need1 = need1 || !derive[j];
+            need1 = need1 || !p.s1.derivable();
         }
         launch_sc1_round_group(k, fold, j1.data(), half, need1, C.stream);
         C.sync();
         for (int j = 0; j < k; ++j) {
             P& p = ps[j];
             HFr gs[3] = {ld_hfr(p.hp), ld_hfr(p.hp + 32), ld_hfr(p.hp + 64)};
-            const HFr ct = p.Cc * p.tau[i - 1];
-            if (derive[j]) {
-                const HFr d1 = (p.claim1 - (p.Cc - ct) * gs[0]) * ct.inv();
-                if (check_derived && !(d1 == gs[1]))
-                    throw SpxError(kSumcheck, "sumcheck 1 round " + std::to_string(i) + ": derived G(1) differs from the device's");
-                gs[1] = d1;
-            }
-            std::vector<HFr> msg = sc1_message(p.Cc, p.tau[i - 1], gs, L);
-            const size_t m0 = p.proof.b.size();
-            p.proof.u64(msg.size());
-            for (auto& e : msg) p.proof.fr(e);
-            p.T.feed(p.proof.b.data() + m0, p.proof.b.size() - m0);
-            const HFr ch = p.T.rand_fr();
-            p.r_x.push_back(ch);
-            const HFr eqc = eq1(p.tau[i - 1], ch);
-            p.claim1 = p.Cc * eqc * quad_at(gs, ch);
-            p.Cc = p.Cc * eqc;
+            p.s1.device_round(gs, check);
             if (fold) {
                 p.cur = j1[j].out;
                 if (j1[j].Eout) p.Ecur = j1[j].Eout;
@@ -2045,63 +1824,20 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         launch_copy_runs_group(k, src.data(), 3, (int)tn, dst.data(), C.stream);
     }
     C.sync();
-    for (auto& p : ps) {
-        std::vector<HFr> tabs[3];
-        {
-            const HFr r = p.r_x.back();
-            for (int m = 0; m < 3; ++m)
-                for (uint32_t b = 0; b < tn / 2; ++b) {
-                    const HFr a0 = ld_hfr(p.hp + 32 * (m * tn + 2 * b)), a1 = ld_hfr(p.hp + 32 * (m * tn + 2 * b + 1));
-                    tabs[m].push_back(a0 + r * (a1 - a0));
-                }
-        }
-        for (int i = L - ht + 1; i <= L; ++i) {  // prove()'s rounds on gathered tables
-            const size_t half = tabs[0].size() / 2;
-            const int c = i - 1;
-            HFr gs[3] = {HFr::zero(), HFr::zero(), HFr::zero()};
-            for (size_t b = 0; b < half; ++b) {
-                HFr e = HFr::one();  // eq(tau_{c+1..L-1}, b)
-                for (int jj = c + 1; jj < L; ++jj) e *= ((b >> (jj - c - 1)) & 1) ? p.tau[jj] : HFr::one() - p.tau[jj];
-                HFr x0[3], x1[3], y[3];
-                for (int m = 0; m < 3; ++m) {
-                    x0[m] = tabs[m][2 * b];
-                    x1[m] = tabs[m][2 * b + 1];
-                    y[m] = x1[m] + x1[m] - x0[m];
-                }
-                gs[0] += (x0[0] * x0[1] - x0[2]) * e;
-                gs[1] += (x1[0] * x1[1] - x1[2]) * e;
-                gs[2] += (y[0] * y[1] - y[2]) * e;
-            }
-            std::vector<HFr> msg = sc1_message(p.Cc, p.tau[c], gs, L);
-            const size_t m1 = p.proof.b.size();
-            p.proof.u64(msg.size());
-            for (auto& e : msg) p.proof.fr(e);
-            p.T.feed(p.proof.b.data() + m1, p.proof.b.size() - m1);
-            const HFr ch = p.T.rand_fr();
-            p.r_x.push_back(ch);
-            p.Cc = p.Cc * eq1(p.tau[c], ch);
-            for (int m = 0; m < 3; ++m) {
-                std::vector<HFr> nt(half);
-                for (size_t b = 0; b < half; ++b) nt[b] = tabs[m][2 * b] + ch * (tabs[m][2 * b + 1] - tabs[m][2 * b]);
-                tabs[m].swap(nt);
-            }
-        }
-        const HFr v[3] = {tabs[0][0], tabs[1][0], tabs[2][0]};
+    for (int j = 0; j < k; ++j) {
+        P& p = ps[j];
+        const std::vector<HFr> vabc = p.s1.tail(p.s1.bind(p.hp, tn));
         // ---- round 4
-        size_t m0 = p.proof.b.size();
-        for (int m = 0; m < 3; ++m) p.proof.fr(v[m]);
-        p.T.feed(p.proof.b.data() + m0, p.proof.b.size() - m0);
-        HFr rabc[3] = {p.T.rand_fr(), p.T.rand_fr(), p.T.rand_fr()};
+        p.io.emit([&](Ser& s) {
+            for (int m = 0; m < 3; ++m) s.fr(vabc[m]);
+        });
+        HFr rabc[3] = {p.io.T.rand_fr(), p.io.T.rand_fr(), p.io.T.rand_fr()};
         // ---- round 5's challenges, staged for one copy (the waits above cover the stage's earlier copy)
-        uint8_t* st = stage + (size_t)32 * (8 * L * (&p - ps.data()) + 2 * L);
-        memcpy(st, p.r_x.data(), 32 * L);
+        uint8_t* st = stage + (size_t)32 * (8 * L * j + 2 * L);
+        memcpy(st, p.s1.r.data(), 32 * L);
         memcpy(st + 32 * L, rabc, 96);
-        m0 = p.proof.b.size();
-        p.proof.u64(2);
-        p.proof.u64((uint64_t)L);
-        p.T.feed(p.proof.b.data() + m0, p.proof.b.size() - m0);
-        p.proof.u64((uint64_t)L);
-        p.claim2 = HFr::zero();
+        p.io.sumcheck_header(2, L);
+        p.s2 = Sumcheck2(p.io, L);
         p.Mc = p.M0;
         p.Zc = p.z;
     }
@@ -2130,29 +1866,17 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
             jb.Zin = p.Zc;
             jb.Mout = fold ? ((i & 1) ? p.M2 : p.M1) : nullptr;
             jb.Zout = fold ? ((i & 1) ? p.Z2 : p.Z1) : nullptr;
-            jb.r = fold ? dev_fr(p.r_y[i - 2]) : Fr{};
+            jb.r = fold ? dev_fr(p.s2.r[i - 2]) : Fr{};
             jb.partial = p.partial;
             jb.ticket = C.ticket + j;
             jb.result3 = p.res_dev;
         }
-        launch_sc2_round_group(k, fold, j2.data(), half, !fold || check_derived, C.stream);
+        launch_sc2_round_group(k, fold, j2.data(), half, !fold || check, C.stream);
         C.sync();
         for (int j = 0; j < k; ++j) {
             P& p = ps[j];
             HFr q[3] = {ld_hfr(p.hp), ld_hfr(p.hp + 32), ld_hfr(p.hp + 64)};
-            if (fold) {
-                const HFr d1 = p.claim2 - q[0];
-                if (check_derived && !(d1 == q[1]))
-                    throw SpxError(kSumcheck, "sumcheck 2 round " + std::to_string(i) + ": derived P(1) differs from the device's");
-                q[1] = d1;
-            }
-            const size_t m0 = p.proof.b.size();
-            p.proof.u64(3);
-            for (int t = 0; t < 3; ++t) p.proof.fr(q[t]);
-            p.T.feed(p.proof.b.data() + m0, p.proof.b.size() - m0);
-            const HFr ch = p.T.rand_fr();
-            p.r_y.push_back(ch);
-            p.claim2 = quad_at(q, ch);
+            p.s2.device_round(q, check);
             if (fold) {
                 p.Mc = j2[j].Mout;
                 p.Zc = j2[j].Zout;
@@ -2166,49 +1890,17 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
             launch_copy_runs_group(k, src.data(), 2, (int)tn, dst.data(), C.stream);
         }
         C.sync();
-        for (auto& p : ps) {
-            const HFr r = p.r_y.back();
-            std::vector<HFr> Mt, Zt;
-            for (uint32_t b = 0; b < tn / 2; ++b) {
-                const HFr m0v = ld_hfr(p.hp + 32 * (2 * b)), m1v = ld_hfr(p.hp + 32 * (2 * b + 1));
-                const HFr z0 = ld_hfr(p.hp + 32 * (tn + 2 * b)), z1 = ld_hfr(p.hp + 32 * (tn + 2 * b + 1));
-                Mt.push_back(m0v + r * (m1v - m0v));
-                Zt.push_back(z0 + r * (z1 - z0));
-            }
-            for (int i = L - ht + 1; i <= L; ++i) {  // prove()'s rounds on gathered tables
-                const size_t half = Mt.size() / 2;
-                HFr q[3] = {HFr::zero(), HFr::zero(), HFr::zero()};
-                for (size_t b = 0; b < half; ++b) {
-                    const HFr m0v = Mt[2 * b], m1v = Mt[2 * b + 1], z0 = Zt[2 * b], z1 = Zt[2 * b + 1];
-                    q[0] += m0v * z0;
-                    q[1] += m1v * z1;
-                    q[2] += (m1v + m1v - m0v) * (z1 + z1 - z0);
-                }
-                const size_t m1 = p.proof.b.size();
-                p.proof.u64(3);
-                for (int t = 0; t < 3; ++t) p.proof.fr(q[t]);
-                p.T.feed(p.proof.b.data() + m1, p.proof.b.size() - m1);
-                const HFr ch = p.T.rand_fr();
-                p.r_y.push_back(ch);
-                std::vector<HFr> nm(half), nz(half);
-                for (size_t b = 0; b < half; ++b) {
-                    nm[b] = Mt[2 * b] + ch * (Mt[2 * b + 1] - Mt[2 * b]);
-                    nz[b] = Zt[2 * b] + ch * (Zt[2 * b + 1] - Zt[2 * b]);
-                }
-                Mt.swap(nm);
-                Zt.swap(nz);
-            }
-        }
+        for (auto& p : ps) p.s2.tail(p.s2.bind(p.hp, tn));
     }
     // ---- round 6: open at r_y
     {
         std::vector<std::vector<HFr>> pts(k);
-        for (int j = 0; j < k; ++j) pts[j] = ps[j].r_y;
+        for (int j = 0; j < k; ++j) pts[j] = ps[j].s2.r;
         open_all(pts);
     }
     std::vector<std::vector<uint8_t>> out(k);
     for (int j = 0; j < k; ++j)
-        if (why[j].empty()) out[j] = std::move(ps[j].proof.b);
+        if (why[j].empty()) out[j] = std::move(ps[j].io.proof.b);
     if (rejected) *rejected = std::move(why);
     C.timings.emplace_back("total_group", tgroup.us());
     return out;
@@ -2218,13 +1910,7 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
 // prove()'s first launch (the index's SpMV, sliced or CSR) into scratch, the check kernel, one wait.
 WitnessReport check_witness(Ctx& C, Index& I, Witness& W) {
     CtxClaim claim(C);
-    struct UnwindDrain {  // a failed exchange leaves nothing running that reads W.z
-        Ctx& C;
-        int pending = std::uncaught_exceptions();
-        ~UnwindDrain() {
-            if (std::uncaught_exceptions() > pending) (void)hipStreamSynchronize(C.stream);
-        }
-    } drain{C};
+    UnwindDrain drain{C, false};  // a failed exchange leaves nothing running that reads W.z
     Comm& comm = *C.comm;
     const int G = comm.size(), rank = comm.rank();
     if (G != I.G || rank != I.rank) invalid("index was built for a different communicator");
@@ -2234,12 +1920,7 @@ WitnessReport check_witness(Ctx& C, Index& I, Witness& W) {
     const uint64_t npart = std::max<uint64_t>(kRoundPartials, I.rows.nchunks);
     C.scratch.ensure(32 * (3 * nl + npart));
     Fr *Az = C.scratch.as<Fr>(), *Bz = Az + nl, *Cz = Bz + nl, *partial = Cz + nl;
-    const Fr* z = W.z.as<Fr>();
-    if (I.rows_sliced.on)
-        launch_spmv_sliced(I.rows_sliced.view(), z, Az, Bz, Cz, I.rows_sliced.entries, C.stream);
-    else
-        launch_sparse3(0, I.rows.view(), z, Az, Bz, Cz, nullptr, nl, I.rows.chunks.as<LongChunk>(), I.rows.nchunks,
-                       I.rows.lrows.as<LongRow>(), I.rows.nlrows, partial, C.stream);
+    launch_rows_spmv(I, W.z.as<Fr>(), Az, Bz, Cz, partial, nl, C.stream);
     const R1csCheckJob job = witness_job(C, 0, Az, Bz, Cz, partial);
     witness_check_launch(C, &job, 1, nl, lo);
     C.sync();

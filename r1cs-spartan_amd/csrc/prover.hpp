@@ -19,17 +19,12 @@
 
 #include "host_ff.hpp"
 #include "kernels.hpp"
+#include "sumcheck_host.hpp"  // SpxError and its codes live with the host-only code that throws them
 #include "transcript.hpp"
 
 namespace spx {
 
-struct SpxError : std::runtime_error {
-    int code;
-    SpxError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-enum { kOk = 0, kInvalidArgument = 1, kSumcheck = 2, kWrongWitness = 3, kSerialization = 4, kDevice = 5 };
-
-#define SPX_HIP(x)                                                                                   \
+#define SPX_HIP(x)                                                                                  \
     do {                                                                                             \
         hipError_t e_ = (x);                                                                         \
         if (e_ != hipSuccess)                                                                        \

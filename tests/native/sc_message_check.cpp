@@ -1,9 +1,9 @@
-// Host check of the sumcheck-1 message stepping (r1cs-spartan_amd/csrc/sc_message.hpp): the
+// Host check of the sumcheck-1 message stepping (r1cs-spartan_amd/csrc/sumcheck_host.hpp): the
 // finite-difference form equals the point-by-point Lagrange form on random inputs. Prints "ok".
 #include <cstdio>
 #include <random>
 
-#include "sc_message.hpp"
+#include "sumcheck_host.hpp"
 
 int main() {
     using F = spx::host::Fr;

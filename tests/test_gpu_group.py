@@ -16,6 +16,9 @@ def _instance(spx, ctx, log_n, log_v, nwit):
     sys.path.insert(0, ROOT)
     import bench
 
+    if log_n == 1:  # below the generator's sizes: z = (1, w), (3 w) (5) = 15 w and (2) (7 w) = 14 w, for every w
+        pk = spx.MLArgumentForR1CS.index(ctx, [[(3, 1)], [(2, 0)]], [[(5, 0)], [(7, 1)]], [[(15, 1)], [(14, 1)]])
+        return None, pk, [spx.Witness(ctx, [1], [0xB0B0 + j]) for j in range(nwit)]
     syn, mats, zs, nnz = bench.synth_instance(spx, 3, log_n, log_v, 0x5EED0000 + log_n, nwit, 0xB0B0)
     pk = spx.IndexPK(ctx, bench.index_from_c(spx, ctx, mats), log_n)
     wits = [spx.Witness(ctx, z[: 32 << log_v], z[32 << log_v :]) for z in zs]
@@ -23,10 +26,11 @@ def _instance(spx, ctx, log_n, log_v, nwit):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("log_n", [6, 16])
+@pytest.mark.parametrize("log_n", [1, 2, 6, 16])
 @pytest.mark.parametrize("mode", ["fs", "injected"])
 def test_group_equals_single(spx, ctx, oc, log_n, mode):
-    log_v = 3
+    # (log_n 1 and 2: a host tail of no round -- 2-entry tables, sumcheck 2's skipped altogether -- and of one)
+    log_v = min(3, log_n - 1)
     syn, pk, wits = _instance(spx, ctx, log_n, log_v, 7)
     want = [spx.MLArgumentForR1CS.prove_witness(pk, w, None, mode=mode, seed=5, commitment_stub=True) for w in wits]
     for k in (2, 3, 8, 16):

@@ -23,7 +23,7 @@ def test_blake2s_kat_and_pieces(tmp_path):
 
 
 def test_sumcheck1_message_stepping(tmp_path):
-    """prover.cpp's sumcheck-1 message (finite differences, sc_message.hpp) equals the point-by-point
+    """the prover's sumcheck-1 message (finite differences, sumcheck_host.hpp) equals the point-by-point
     Lagrange form of P(t) = C eq(tau, t) G(t) (prover.rs:199-207 with the degree-3 factorisation)"""
     cxx = shutil.which("g++") or shutil.which("clang++")
     if not cxx:
