@@ -20,6 +20,7 @@
  *   spx_pp_generate      MLProofForR1CS::setup / MLPolyCommit::keygen  src/ahp/setup.rs:13-16, src/commitment/setup.rs:27-105
  *   spx_commit           MLPolyCommit::commit                     src/commitment/commit.rs:17-29
  *   spx_open             MLPolyCommit::open                       src/commitment/open.rs:19-58
+ *   spx_pc_verify        MLPolyCommit::verify                     src/commitment/verify.rs:12-45
  *   spx_sum_over_y       MatrixExtension::sum_over_y              src/data_structures/r1cs_reader.rs:75-85
  *   spx_eval_on_x        MatrixExtension::eval_on_x               src/data_structures/r1cs_reader.rs:91-117
  *   spx_msm_g1 / _g2     ark-ec VariableBaseMSM::multi_scalar_mul (called at commit.rs:25, open.rs:49)
@@ -259,7 +260,8 @@ int spx_verify_many_coeffs(const uint8_t *const *v, const size_t *nv, const uint
  * out[1] pairs given to the Miller loop by the batched path (log_n + 2 per batch), out[2] proofs sent to
  * the single-proof path, out[3] points decompressed on the GPU */
 int spx_verify_stats(spx_ctx *ctx, uint64_t out[4]);
-/* VerifierParameter of a keygen-generated PP (spx_pp_generate; setup.rs:91-101), uncompressed bytes */
+/* VerifierParameter of a keygen-generated PP (spx_pp_generate; setup.rs:91-101) or of a view of one,
+ * from the trapdoor, uncompressed bytes. A loaded parameter has no trapdoor: use spx_pp_derive_vp. */
 int spx_vp_from_pp(spx_pp *pp, uint8_t *out, size_t cap, size_t *len);
 /* prod_i e(P_i, Q_i) == 1 over n pairs (uncompressed G1 96 B / G2 192 B each); host only, no GPU
  * (E::product_of_pairings as used by verify.rs:12-45) */
@@ -404,6 +406,56 @@ int spx_point_in_subgroup_host(int curve /* 1 | 2 */, const uint8_t *pt_uncompre
  * bad and first may each be NULL. Every rank of a sharded context holds the complete raw levels, so the
  * call works on any context of the public parameter's device. */
 int spx_pp_check_subgroup(spx_ctx *ctx, spx_pp *pp, uint64_t *bad, uint64_t first[3]);
+
+/* ---- public-parameter structure, derived verifier parameter, views ("Public-parameter
+ * structure and views") ----
+ * With bit 0 of x paired with t_i, the levels of a well-formed parameter satisfy
+ *   powers_of_g[i][2b] + powers_of_g[i][2b+1] = powers_of_g[i+1][b]   (the last level's pair sums to g),
+ *   sum_b powers_of_g[i][2b+1] = g^{t_i} = vp.g_mask_random[i],
+ * the same for powers_of_h and h, and the parameter of nv' < nv variables is levels nv - nv' .. nv - 1. */
+
+/* MLPolyCommit::verify (commitment/verify.rs:12-45). Host only, no GPU. com56 = spx_commit's output,
+ * proof = spx_open's proof_out (96 + 8 + 96 nv bytes), point = nv canonical Fr. *accepted = 1 | 0.
+ * Malformed bytes: SPX_SERIALIZATION; nv != vp.nv or a wrong length: SPX_INVALID_ARGUMENT. */
+int spx_pc_verify(const uint8_t *vp, size_t vp_len, const uint8_t com56[56], const uint8_t *point, int nv,
+                  const uint8_t value[32], const uint8_t *proof, size_t proof_len, int *accepted);
+
+/* VerifierParameter of ANY public parameter (loaded, generated, or a view), uncompressed, in
+ * spx_vp_from_pp's format: g_mask_random[i] = sum of the odd-index points of powers_of_g[i], summed on
+ * the ctx's GPU. For a generated parameter the bytes equal spx_vp_from_pp's. The call does not run the
+ * structure check: the result is meaningful for a parameter that passes spx_pp_check_structure. */
+int spx_pp_derive_vp(spx_ctx *ctx, spx_pp *pp, uint8_t *out, size_t cap, size_t *len);
+
+/* Structure of a public parameter, in two stages, on the ctx's GPU.
+ * Stage 1 (exact): the fold relation for every pair of every level of both curves.
+ *   *bad = number of failing pairs.
+ *   first = {curve 1 | 2, level, pair index b} of the lowest failing pair, in the order G1 levels, G2
+ *   levels, by level, then b (pair b of level i is points 2b, 2b+1 against point b of level i+1; the
+ *   last level's only pair is against g / h).
+ * Stage 2 (only if stage 1 passed; otherwise *opening_ok = -1): a commitment to a pseudo-random table,
+ *   opened at a pseudo-random point, must verify (spx_pc_verify's equation) under the derived VP.
+ *   *opening_ok = 1 | 0.
+ * entropy32 seeds stage 2's table and point. With NULL a fixed seed is used: that finds damage, not an
+ * adversary who knows the seed.
+ * Returns SPX_OK, or SPX_SERIALIZATION with spx_last_error naming the pair ("powers_of_h level 3 pair 17:
+ * points 34 + 35 != level 4 point 17 (2 such pairs)") or "opening self-test failed".
+ * bad, first and opening_ok may each be NULL. Afterwards spx_last_timings holds the two stages' wall
+ * time and the device time of stage 1's two kernels, in microseconds. */
+int spx_pp_check_structure(spx_ctx *ctx, spx_pp *pp, const uint8_t *entropy32, uint64_t *bad,
+                           uint64_t first[3], int *opening_ok);
+
+/* The public parameter of nv variables (1 <= nv <= parent's) that a larger one contains: levels
+ * parent_nv - nv .. parent_nv - 1 of both curves, and g, h. The handle behaves as a PP of nv variables in
+ * every call that takes an spx_pp. It borrows the parent's device storage (the raw levels and the G2
+ * opening tables, with the parent's window bits; spx_pp_window_plan reports them) and builds only its own
+ * G1 commitment table; with nv == the parent's it shares that too. Ownership of the storage is shared: the
+ * parent may be freed first. A view of a view refers to the root's storage. ctx must be on the parent's
+ * device (SPX_INVALID_ARGUMENT otherwise, as for nv out of range or a NULL handle). */
+int spx_pp_view(spx_ctx *ctx, spx_pp *parent, int nv, spx_pp **out);
+
+/* out[0] device bytes this handle allocated itself, out[1] device bytes it borrows from a parent (0 for a
+ * loaded / generated PP), out[2] handles alive on the storage it uses (itself included). No GPU call. */
+int spx_pp_mem_info(spx_pp *pp, uint64_t out[3]);
 /* Subgroup check of proof points in spx_verify and spx_verify_many on this context: 0 = off (the
  * default: every status and message as before), 1 = on, -1 = the process default (SPX_SUBGROUP_CHECK=1
  * -> on, else off). On: spx_verify tests the commitment and every point of the two opening proofs right

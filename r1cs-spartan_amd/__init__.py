@@ -162,6 +162,11 @@ EXPORTED = [
     "spx_witness_check_stats",
     "spx_commit",
     "spx_open",
+    "spx_pc_verify",
+    "spx_pp_derive_vp",
+    "spx_pp_check_structure",
+    "spx_pp_view",
+    "spx_pp_mem_info",
 ]
 
 _lib = None
@@ -293,6 +298,13 @@ def lib():
     L.spx_msm_g2.argtypes = [vp, u8p, u8p, sz, ctypes.c_void_p]
     L.spx_commit.argtypes = [vp, vp, u8p, ctypes.c_int, ctypes.c_void_p]
     L.spx_open.argtypes = [vp, vp, u8p, ctypes.c_int, u8p, ctypes.c_void_p, ctypes.c_void_p]
+    if hasattr(L, "spx_pp_view") or not os.environ.get("SPX_LIB_PATH"):  # A/B builds may predate it
+        pu64 = ctypes.POINTER(ctypes.c_uint64)
+        L.spx_pc_verify.argtypes = [u8p, sz, u8p, u8p, ctypes.c_int, u8p, u8p, sz, ctypes.POINTER(ctypes.c_int)]
+        L.spx_pp_derive_vp.argtypes = [vp, vp, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
+        L.spx_pp_check_structure.argtypes = [vp, vp, u8p, pu64, pu64, ctypes.POINTER(ctypes.c_int)]
+        L.spx_pp_view.argtypes = [vp, vp, ctypes.c_int, ctypes.POINTER(vp)]
+        L.spx_pp_mem_info.argtypes = [vp, pu64]
     for name in EXPORTED:
         if name not in ("spx_last_error", "spx_version", "spx_proof_size"):
             if os.environ.get("SPX_LIB_PATH") and not hasattr(L, name):
@@ -638,15 +650,61 @@ class PublicParameter:
         self.ctx, self.h, self.nv = ctx, h, nv
 
     @staticmethod
-    def load(ctx, data, check_subgroup=False):
+    def load(ctx, data, check_subgroup=False, check_structure=False):
         """check_subgroup: also test every point for membership of its prime-order subgroup
-        (spx_pp_check_subgroup) and raise SerializationError naming the first one outside it"""
+        (spx_pp_check_subgroup) and raise SerializationError naming the first one outside it.
+        check_structure: also run spx_pp_check_structure (fixed seed) and raise SerializationError naming
+        the first pair of points that breaks the fold relation, or the failed opening self-test"""
         h = ctypes.c_void_p()
         _check(lib().spx_pp_load(ctx.h, bytes(data), len(data), ctypes.byref(h)))
         pp = PublicParameter(ctx, h, int.from_bytes(data[:8], "little"))
         if check_subgroup:
             pp.check_subgroup()
+        if check_structure:
+            pp.check_structure()
         return pp
+
+    def view(self, nv, ctx=None):
+        """The public parameter of nv <= self.nv variables that this one contains (spx_pp_view): it borrows
+        this parameter's device storage and builds only its own commitment table. Either handle may be
+        dropped first. ctx: another context on the same device (default: this parameter's)."""
+        ctx = ctx or self.ctx
+        h = ctypes.c_void_p()
+        _check(lib().spx_pp_view(ctx.h, self.h, int(nv), ctypes.byref(h)))
+        return PublicParameter(ctx, h, int(nv))
+
+    def derive_vp(self):
+        """VerifierParameter bytes (uncompressed) of any public parameter, from the odd-index sums of its G1
+        levels (spx_pp_derive_vp). Meaningful for a parameter that passes check_structure."""
+        cap = 8 + 96 + 192 + 8 + 96 * 64
+        out = ctypes.create_string_buffer(cap)
+        n = ctypes.c_size_t(0)
+        _check(lib().spx_pp_derive_vp(self.ctx.h, self.h, out, cap, ctypes.byref(n)))
+        return out.raw[: n.value]
+
+    def check_structure(self, entropy=None, strict=True):
+        """The fold relation of every pair of points of every level, then an opening self-test under the
+        derived VP (spx_pp_check_structure). entropy: 32 bytes seeding the self-test (None: a fixed seed).
+        Returns (bad, first, opening_ok): the number of failing pairs, the lowest one as (curve, level, pair)
+        or None, and 1 | 0 (-1: not run, stage 1 failed). strict: raise SerializationError instead of
+        returning a failure."""
+        if entropy is not None and len(entropy) != 32:
+            raise InvalidArgument("entropy must be 32 bytes")
+        bad = ctypes.c_uint64(0)
+        first = (ctypes.c_uint64 * 3)()
+        ok = ctypes.c_int(-1)
+        rc = lib().spx_pp_check_structure(self.ctx.h, self.h, None if entropy is None else bytes(entropy),
+                                          ctypes.byref(bad), first, ctypes.byref(ok))
+        if rc != 0 and (strict or rc != 4):
+            _check(rc)
+        return bad.value, (tuple(int(x) for x in first) if bad.value else None), ok.value
+
+    def mem_info(self):
+        """[device bytes this handle allocated, device bytes it borrows from a parent, handles alive on its
+        storage] (spx_pp_mem_info)"""
+        out = (ctypes.c_uint64 * 3)()
+        _check(lib().spx_pp_mem_info(self.h, out))
+        return [int(x) for x in out]
 
     def check_subgroup(self, strict=True):
         """Membership of every G1 and G2 point (the raw levels on the GPU, g and h on the host;
@@ -1015,7 +1073,8 @@ class ConstraintSystem:
 
 
 def verifier_parameter(pp):
-    """VerifierParameter bytes (uncompressed) of a keygen-generated PP (setup.rs:91-101)."""
+    """VerifierParameter bytes (uncompressed) of a keygen-generated PP (setup.rs:91-101), or of a view of one.
+    A loaded parameter has no trapdoor: PublicParameter.derive_vp()."""
     cap = 8 + 96 + 192 + 8 + 96 * 64
     out = ctypes.create_string_buffer(cap)
     n = ctypes.c_size_t(0)
@@ -1184,6 +1243,15 @@ class MLPolyCommit:
         pf = ctypes.create_string_buffer(96 + 8 + 96 * nv)
         _check(lib().spx_open(pp.ctx.h, pp.h, tb, nv, pb, ev, pf))
         return ev.raw, pf.raw
+
+    @staticmethod
+    def verify(vp, commitment, point, value, proof):
+        """MLPolyCommit::verify (commitment/verify.rs:12-45) on the host (spx_pc_verify): True | False"""
+        pb, vb = _as_bytes(point), _as_bytes(value)
+        ok = ctypes.c_int(0)
+        _check(lib().spx_pc_verify(bytes(vp), len(vp), bytes(commitment), pb, len(pb) // 32, vb, bytes(proof),
+                                   len(proof), ctypes.byref(ok)))
+        return bool(ok.value)
 
 
 def msm_window_plan(size):

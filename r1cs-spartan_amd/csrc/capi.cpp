@@ -646,6 +646,54 @@ int spx_vp_from_pp(spx_pp* pp, uint8_t* out, size_t cap, size_t* len) {
         copy_out(spx::vp_serialize(spx::vp_from_pp(*pp->p)), out, cap, len);
     });
 }
+int spx_pp_derive_vp(spx_ctx* ctx, spx_pp* pp, uint8_t* out, size_t cap, size_t* len) {
+    return guard([&] {
+        if (!pp) spx::invalid("null public parameter");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        copy_out(spx::vp_serialize(spx::pp_derive_vp(*ctx->c, *pp->p)), out, cap, len);
+    });
+}
+int spx_pc_verify(const uint8_t* vp, size_t vp_len, const uint8_t com56[56], const uint8_t* point, int nv,
+                  const uint8_t value[32], const uint8_t* proof, size_t proof_len, int* accepted) {
+    return guard([&] {
+        if (!vp || !com56 || (nv > 0 && !point) || !value || !proof || !accepted) spx::invalid("null argument");
+        *accepted = spx::pc_verify(spx::vp_load(vp, vp_len), com56, point, nv, value, proof, proof_len) ? 1 : 0;
+    });
+}
+int spx_pp_check_structure(spx_ctx* ctx, spx_pp* pp, const uint8_t* entropy32, uint64_t* bad, uint64_t first[3],
+                           int* opening_ok) {
+    return guard([&] {
+        if (!pp) spx::invalid("null public parameter");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        const spx::PPStructureReport r = spx::pp_check_structure(*ctx->c, *pp->p, entropy32);
+        // spx_last_timings: the two stages' wall time and the fold kernels' device time (us), at fixed positions
+        ctx->c->timings.clear();
+        ctx->c->timings.emplace_back("pp_fold_check", r.stage_ms[0] * 1000.0);
+        ctx->c->timings.emplace_back("pp_opening_test", r.stage_ms[1] * 1000.0);
+        ctx->c->timings.emplace_back("pp_fold_kernels", r.fold_kernel_ms * 1000.0);
+        if (bad) *bad = r.bad;
+        if (first)
+            for (int i = 0; i < 3; ++i) first[i] = r.first[i];
+        if (opening_ok) *opening_ok = r.opening_ok;
+        if (!r.message.empty()) throw spx::SpxError(spx::kSerialization, r.message);
+    });
+}
+int spx_pp_view(spx_ctx* ctx, spx_pp* parent, int nv, spx_pp** out) {
+    return guard([&] {
+        if (!parent || !out) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        *out = new spx_pp{ctx, spx::pp_view(*ctx->c, *parent->p, nv)};
+    });
+}
+int spx_pp_mem_info(spx_pp* pp, uint64_t out[3]) {
+    return guard([&] {
+        if (!pp || !out) spx::invalid("null argument");
+        spx::pp_mem_info(*pp->p, out);
+    });
+}
 int spx_verify(spx_ctx* ctx, spx_pk* idx, const uint8_t* v, size_t nv, const uint8_t* proof, size_t len,
                const uint8_t* vp, size_t vp_len, const spx_prove_opts* opts) {
     return guard([&] {

@@ -376,4 +376,19 @@ void launch_in_subgroup_g2(const G2Aff* pts, uint64_t n, uint8_t* ok, hipStream_
 // out2[0] += the number of zeros in ok[0 .. n), out2[1] = min(out2[1], the first zero's index)
 void launch_ok_scan(const uint8_t* ok, uint64_t n, uint64_t* out2, hipStream_t s);
 
+// ---- pp_kernels.hip ("Public-parameter structure and views")
+// pts: the 2^(nv+1) - 2 raw points of an nv-variable parameter, levels contiguous (level i: 2^(nv-i) points,
+// affine Montgomery, (0, 0) = infinity). ok[j] = 1 if pair j of the flat array (points 2j, 2j + 1; 2^nv - 1
+// pairs) sums to its target: pair b of level i against point b of level i + 1, the last level's only pair
+// against `last` (g / h). One pair per lane, blocks of kPPFoldLanes.
+static constexpr uint32_t kPPFoldLanes = 64;
+void launch_fold_check_g1(const G1Aff* pts, int nv, const G1Aff& last, uint8_t* ok, hipStream_t s);
+void launch_fold_check_g2(const G2Aff* pts, int nv, const G2Aff& last, uint8_t* ok, hipStream_t s);
+// out[i] = sum_b pts_i[2b + 1] for every level i of the same array, as XYZZ (ZZ = 0: infinity): per level
+// odd_sum_blocks(nv) blocks of kPPSumThreads write partials to part (nv * odd_sum_blocks(nv) XYZZ), and a
+// second pass of one block per level sums them.
+static constexpr uint32_t kPPSumThreads = 256, kPPSumMaxBlocks = 256;
+uint32_t odd_sum_blocks(int nv);
+void launch_odd_sum_g1(const G1Aff* pts, int nv, G1Xyzz* part, G1Xyzz* out, hipStream_t s);
+
 }  // namespace spx

@@ -220,8 +220,8 @@ void pp_preprocess(Ctx& C, PP& P) {
     const int wide = msm_wide_min_log();
     P.g1_c = window_bits_for(n, wide);
     P.g1_W = windows_for(P.g1_c);
-    P.g1_pre.alloc(sizeof(G1Slot) * n * P.g1_W);
-    precompute_level(C, P.g1_level(0), n, false, P.g1_c, P.g1_W, P.g1_pre.as<G1Slot>());
+    P.g1_pre = std::make_shared<DevMem>(sizeof(G1Slot) * n * P.g1_W);
+    precompute_level(C, P.g1_level(0), n, false, P.g1_c, P.g1_W, P.g1_pre->as<G1Slot>());
     P.g2_off.assign(nv + 1, 0);
     P.g2_c = g2_window_plan(nv, wide);
     P.g2_W.assign(nv, 0);
@@ -233,14 +233,14 @@ void pp_preprocess(Ctx& C, PP& P) {
         tot += cnt * P.g2_W[i];
     }
     P.g2_off[nv] = tot;
-    P.g2_pre.alloc(sizeof(G2Aff) * std::max<uint64_t>(tot, 1));
+    P.store->g2_pre.alloc(sizeof(G2Aff) * std::max<uint64_t>(tot, 1));
     for (int i = 0; i < nv; ++i) {
         uint64_t cnt = 1ull << (nv - i - 1);
-        precompute_level(C, P.g2_level(i), cnt, true, P.g2_c[i], P.g2_W[i], P.g2_pre.as<G2Aff>() + P.g2_off[i]);
+        precompute_level(C, P.g2_level(i), cnt, true, P.g2_c[i], P.g2_W[i], P.store->g2_pre.as<G2Aff>() + P.g2_off[i]);
     }
 }
 
-static void pp_alloc_raw(PP& P, int nv) {
+static void pp_alloc_raw(PP& P, int nv, int device) {
     P.nv = nv;
     P.lvl_off.assign(nv + 1, 0);
     uint64_t tot = 0;
@@ -249,8 +249,10 @@ static void pp_alloc_raw(PP& P, int nv) {
         tot += 1ull << (nv - i);
     }
     P.lvl_off[nv] = tot;
-    P.g1_raw_mem.alloc(sizeof(G1Aff) * std::max<uint64_t>(tot, 1));
-    P.g2_raw_mem.alloc(sizeof(G2Aff) * std::max<uint64_t>(tot, 1));
+    P.store = std::make_shared<PPStore>();
+    P.store->device = device;
+    P.store->g1_raw_mem.alloc(sizeof(G1Aff) * std::max<uint64_t>(tot, 1));
+    P.store->g2_raw_mem.alloc(sizeof(G2Aff) * std::max<uint64_t>(tot, 1));
 }
 
 std::unique_ptr<PP> pp_load(Ctx& C, const uint8_t* b, size_t len) {
@@ -269,7 +271,7 @@ std::unique_ptr<PP> pp_load(Ctx& C, const uint8_t* b, size_t len) {
     uint64_t nv = u64();
     if (nv < 1 || nv > (uint64_t)kMaxLogN) throw SpxError(kSerialization, "bad public parameter nv (1..26 supported)");
     if (u64() != nv) throw SpxError(kSerialization, "powers_of_g length != nv");
-    pp_alloc_raw(*P, (int)nv);
+    pp_alloc_raw(*P, (int)nv, C.device);
     std::vector<size_t> g1_pos(nv), g2_pos(nv);
     for (uint64_t i = 0; i < nv; ++i) {
         if (u64() != (1ull << (nv - i))) throw SpxError(kSerialization, "powers_of_g level size");
@@ -293,8 +295,8 @@ std::unique_ptr<PP> pp_load(Ctx& C, const uint8_t* b, size_t len) {
     }
     DevMem err(sizeof(int));
     SPX_HIP(hipMemsetAsync(err.p, 0, sizeof(int), C.stream));
-    launch_points_from_bytes_g1(P->g1_raw_mem.as<G1Aff>(), P->lvl_off[nv], err.as<int>(), C.stream);
-    launch_points_from_bytes_g2(P->g2_raw_mem.as<G2Aff>(), P->lvl_off[nv], err.as<int>(), C.stream);
+    launch_points_from_bytes_g1(P->g1_raw(), P->lvl_off[nv], err.as<int>(), C.stream);
+    launch_points_from_bytes_g2(P->g2_raw(), P->lvl_off[nv], err.as<int>(), C.stream);
     int herr = 0;
     SPX_HIP(hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, C.stream));
     C.sync();
@@ -374,7 +376,7 @@ std::unique_ptr<PP> pp_generate(Ctx& C, int nv, uint64_t seed) {
     P->g = host::jac_to_affine(host::jac_mul(host::jac_from(host::g1_generator()), c));
     hs.to_canon(c);
     P->h = host::jac_to_affine(host::jac_mul(host::jac_from(host::g2_generator()), c));
-    pp_alloc_raw(*P, nv);
+    pp_alloc_raw(*P, nv, C.device);
     const uint64_t tot = P->lvl_off[nv];
     // eq(t[i..], x) scalars for every level (setup.rs:37-60), Montgomery
     DevMem tdev(32 * nv), scal(32 * tot), lo(32 << 14), hi(32 << 14);
@@ -386,14 +388,14 @@ std::unique_ptr<PP> pp_generate(Ctx& C, int nv, uint64_t seed) {
         auto tg = fixed_base_table(P->g);
         DevMem tab(sizeof(G1Aff) * tg.size()), tmp(2 * sizeof(G1Aff) * tot);
         upload_affine(tg, tab.as<G1Aff>(), C.stream);
-        fixed_base_g1(tab.as<G1Aff>(), scal.as<Fr>(), tot, P->g1_raw_mem.as<G1Aff>(), tmp.p, C.stream);
+        fixed_base_g1(tab.as<G1Aff>(), scal.as<Fr>(), tot, P->g1_raw(), tmp.p, C.stream);
         C.sync();
     }
     {
         auto th = fixed_base_table(P->h);
         DevMem tab(sizeof(G2Aff) * th.size()), tmp(2 * sizeof(G2Aff) * tot);
         upload_affine(th, tab.as<G2Aff>(), C.stream);
-        fixed_base_g2(tab.as<G2Aff>(), scal.as<Fr>(), tot, P->g2_raw_mem.as<G2Aff>(), tmp.p, C.stream);
+        fixed_base_g2(tab.as<G2Aff>(), scal.as<Fr>(), tot, P->g2_raw(), tmp.p, C.stream);
         C.sync();
     }
     pp_preprocess(C, *P);
@@ -407,8 +409,8 @@ std::vector<uint8_t> pp_serialize(Ctx& C, const PP& P) {
     for (int i = 0; i < nv; ++i) need += 16 + (96 + 192) * (1ull << (nv - i));
     std::vector<uint8_t> out(need);
     DevMem t1(sizeof(G1Aff) * tot), t2(sizeof(G2Aff) * tot);
-    SPX_HIP(hipMemcpyAsync(t1.p, P.g1_raw_mem.p, sizeof(G1Aff) * tot, hipMemcpyDeviceToDevice, C.stream));
-    SPX_HIP(hipMemcpyAsync(t2.p, P.g2_raw_mem.p, sizeof(G2Aff) * tot, hipMemcpyDeviceToDevice, C.stream));
+    SPX_HIP(hipMemcpyAsync(t1.p, P.g1_raw(), sizeof(G1Aff) * tot, hipMemcpyDeviceToDevice, C.stream));
+    SPX_HIP(hipMemcpyAsync(t2.p, P.g2_raw(), sizeof(G2Aff) * tot, hipMemcpyDeviceToDevice, C.stream));
     launch_points_to_canon_g1(t1.as<G1Aff>(), tot, C.stream);
     launch_points_to_canon_g2(t2.as<G2Aff>(), tot, C.stream);
     std::vector<uint8_t> h1(sizeof(G1Aff) * tot), h2(sizeof(G2Aff) * tot);
@@ -969,7 +971,7 @@ static void commit_launch(Ctx& C, PP& P, const Fr* z, uint64_t n, const MsmShard
     inst.W = (uint32_t)P.g1_W;
     const size_t ob = msm_out_bytes(false, 1);
     void* out = C.buf(Ctx::kSlotCommit, ob);
-    msm_run_g1(C.msm, &inst, 1, P.g1_pre.as<G1Slot>(), z, out, C.stream, sh);
+    msm_run_g1(C.msm, &inst, 1, P.g1_tab(), z, out, C.stream, sh);
     SPX_HIP(hipMemcpyAsync(C.pin_at(Ctx::kPinCommit, ob, 2 << 10), out, ob, hipMemcpyDeviceToHost, C.stream));
 }
 static Affine<HFq> commit_finish(Ctx& C, PP& P, const Fr* z, uint64_t n, Comm& comm) {
@@ -1020,7 +1022,7 @@ static void lvl0_launch(Ctx& C, PP& P, const Fr* z, int L, const MsmShard& sh, b
     I.W = (uint32_t)P.g2_W[0];
     const size_t ob = msm_out_bytes(true, 1);
     void* out = C.buf(Ctx::kSlotLvl0Out, ob);
-    msm_run_g2(ws, &I, 1, P.g2_pre.as<G2Aff>(), q, out, st, sh);
+    msm_run_g2(ws, &I, 1, P.g2_pre(), q, out, st, sh);
     SPX_HIP(hipMemcpyAsync(C.pin_at(Ctx::kPinLvl0, ob, 4 << 10), out, ob, hipMemcpyDeviceToHost, st));
 }
 static Affine<HFq2> lvl0_finish(Ctx& C, PP& P, const Fr* z, int L, Comm& comm, bool on_side = false) {
@@ -1119,7 +1121,7 @@ static OpenOut open_z(Ctx& C, PP& P, const Fr* z, int L, const std::vector<HFr>&
         MsmShard sh = shard_of(comm);
         sh.dense = attempt > 0;
         if (nm) {
-            msm_run_g2(C.msm, insts.data(), nm, P.g2_pre.as<G2Aff>(), q, out, C.stream, sh);
+            msm_run_g2(C.msm, insts.data(), nm, P.g2_pre(), q, out, C.stream, sh);
             SPX_HIP(hipMemcpyAsync(h, out, ob, hipMemcpyDeviceToHost, C.stream));
         }
         if (!attempt) SPX_HIP(hipMemcpyAsync(h + ob, rin, 32, hipMemcpyDeviceToHost, C.stream));
@@ -2713,8 +2715,8 @@ PPSubgroupReport pp_check_subgroup(Ctx& C, const PP& P) {
     const uint64_t init[4] = {0, ~0ull, 0, ~0ull};
     uint64_t got[4];
     SPX_HIP(hipMemcpyAsync(res.p, init, 32, hipMemcpyHostToDevice, C.stream));
-    launch_in_subgroup_g1(P.g1_raw_mem.as<G1Aff>(), tot, ok.as<uint8_t>(), C.stream);
-    launch_in_subgroup_g2(P.g2_raw_mem.as<G2Aff>(), tot, ok.as<uint8_t>() + tot, C.stream);
+    launch_in_subgroup_g1(P.g1_raw(), tot, ok.as<uint8_t>(), C.stream);
+    launch_in_subgroup_g2(P.g2_raw(), tot, ok.as<uint8_t>() + tot, C.stream);
     launch_ok_scan(ok.as<uint8_t>(), tot, res.as<uint64_t>(), C.stream);
     launch_ok_scan(ok.as<uint8_t>() + tot, tot, res.as<uint64_t>() + 2, C.stream);
     SPX_HIP(hipMemcpyAsync(got, res.p, 32, hipMemcpyDeviceToHost, C.stream));
@@ -2747,6 +2749,180 @@ PPSubgroupReport pp_check_subgroup(Ctx& C, const PP& P) {
     r.message = "public parameter point outside the prime-order subgroup: " + r.message + " (" +
                 std::to_string(r.bad) + " such point" + (r.bad == 1 ? "" : "s") + ")";
     return r;
+}
+
+// ---- public-parameter structure, derived verifier parameter, views
+VP pp_derive_vp(Ctx& C, const PP& P) {
+    const int nv = P.nv;
+    const uint32_t nblk = odd_sum_blocks(nv);
+    DevMem part(sizeof(G1Xyzz) * nv * nblk), out(sizeof(G1Xyzz) * nv);
+    launch_odd_sum_g1(P.g1_raw(), nv, part.as<G1Xyzz>(), out.as<G1Xyzz>(), C.stream);
+    std::vector<uint8_t> h(out.bytes);
+    SPX_HIP(hipMemcpyAsync(h.data(), out.p, out.bytes, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    VP V;
+    V.nv = nv;
+    V.g = P.g;
+    V.h = P.h;
+    for (int i = 0; i < nv; ++i)
+        V.g_mask.push_back(host::jac_to_affine(xyzz_bytes_to_jac<HFq>(h.data() + sizeof(G1Xyzz) * i)));
+    return V;
+}
+
+bool pc_verify(const VP& V, const uint8_t com56[56], const uint8_t* point, int nv, const uint8_t value[32],
+               const uint8_t* proof, size_t proof_len) {
+    if (nv != V.nv) invalid("point length != nv of the verifier parameter");
+    if (proof_len != 96 + 8 + (size_t)96 * nv) invalid("opening proof length != 96 + 8 + 96 nv");
+    uint64_t cnv;
+    memcpy(&cnv, com56, 8);
+    if (cnv != (uint64_t)nv) invalid("commitment nv != nv of the verifier parameter");
+    host::Affine<HFq> com{HFq::zero(), HFq::zero(), false};
+    if (!host::g1_decompress(com, com56 + 8)) throw SpxError(kSerialization, "invalid G1 point");
+    std::vector<HFr> pt(nv);
+    for (int i = 0; i < nv; ++i)
+        if (!host::fr_from_bytes(pt[i], point + 32 * i)) throw SpxError(kSerialization, "non-canonical point");
+    HFr val;
+    if (!host::fr_from_bytes(val, value)) throw SpxError(kSerialization, "non-canonical field element");
+    ProofReader R{proof, proof_len};
+    OpenProof op;
+    op.eval = val;
+    op.h = R.g2();
+    if (R.u64() != (uint64_t)nv) throw SpxError(kSerialization, "bad opening proof length");
+    for (int i = 0; i < nv; ++i) op.proofs.push_back(R.g2());
+    return mkzg_check(V, com, pt, val, op);
+}
+
+template <class A, class F>
+static A dev_affine(const Affine<F>& a) {  // infinity: the (0, 0) sentinel
+    static_assert(sizeof(A) == 2 * sizeof(F), "layout");
+    A d;
+    memset(&d, 0, sizeof(A));
+    if (!a.inf) {
+        memcpy((uint8_t*)&d, &a.x, sizeof(F));
+        memcpy((uint8_t*)&d + sizeof(F), &a.y, sizeof(F));
+    }
+    return d;
+}
+
+PPStructureReport pp_check_structure(Ctx& C, PP& P, const uint8_t* entropy32) {
+    const int nv = P.nv;
+    const uint64_t pairs = P.lvl_off[nv] / 2;
+    PPStructureReport r;
+    Timer t1;
+    {
+        // every pair of every level of a curve in one launch (the levels are contiguous), then the count
+        // of the failing pairs and the lowest one's flat index
+        DevMem ok(2 * pairs), res(32);
+        const uint64_t init[4] = {0, ~0ull, 0, ~0ull};
+        uint64_t got[4];
+        SPX_HIP(hipMemcpyAsync(res.p, init, 32, hipMemcpyHostToDevice, C.stream));
+        hipEvent_t ev[2];  // device time of the two fold kernels (tools/pp_bench.py)
+        SPX_HIP(hipEventCreate(&ev[0]));
+        SPX_HIP(hipEventCreate(&ev[1]));
+        SPX_HIP(hipEventRecord(ev[0], C.stream));
+        launch_fold_check_g1(P.g1_raw(), nv, dev_affine<G1Aff>(P.g), ok.as<uint8_t>(), C.stream);
+        launch_fold_check_g2(P.g2_raw(), nv, dev_affine<G2Aff>(P.h), ok.as<uint8_t>() + pairs, C.stream);
+        SPX_HIP(hipEventRecord(ev[1], C.stream));
+        launch_ok_scan(ok.as<uint8_t>(), pairs, res.as<uint64_t>(), C.stream);
+        launch_ok_scan(ok.as<uint8_t>() + pairs, pairs, res.as<uint64_t>() + 2, C.stream);
+        SPX_HIP(hipMemcpyAsync(got, res.p, 32, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        float kms = 0;
+        (void)hipEventElapsedTime(&kms, ev[0], ev[1]);
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+        r.fold_kernel_ms = kms;
+        r.bad = got[0] + got[2];
+        if (r.bad) {
+            const int c = got[0] ? 0 : 1;
+            const uint64_t j = got[2 * c + 1];  // flat pair index: level i starts at pair lvl_off[i] / 2
+            int lvl = 0;
+            while (2 * j >= P.lvl_off[lvl + 1]) ++lvl;
+            const uint64_t b = j - P.lvl_off[lvl] / 2;
+            r.first[0] = (uint64_t)c + 1, r.first[1] = (uint64_t)lvl, r.first[2] = b;
+            r.message = std::string(c ? "powers_of_h" : "powers_of_g") + " level " + std::to_string(lvl) + " pair " +
+                        std::to_string(b) + ": points " + std::to_string(2 * b) + " + " + std::to_string(2 * b + 1) + " != " +
+                        (lvl + 1 < nv ? "level " + std::to_string(lvl + 1) + " point " + std::to_string(b)
+                                      : std::string(c ? "h" : "g")) +
+                        " (" + std::to_string(r.bad) + " such pair" + (r.bad == 1 ? "" : "s") + ")";
+        }
+    }
+    r.stage_ms[0] = t1.us() / 1000.0;
+    if (r.bad) return r;
+    // Stage 2: the opening identity for a pseudo-random table at a pseudo-random point, under the derived VP.
+    // Four SplitMix64 streams, one per limb, each seeded with a word of the entropy.
+    Timer t2;
+    SplitMix64 rng[4];
+    for (int k = 0; k < 4; ++k) {
+        uint64_t w = 0x5350585f50505f32ULL * (k + 1);
+        if (entropy32) memcpy(&w, entropy32 + 8 * k, 8), w ^= 0x9E3779B97F4A7C15ULL * (k + 1);
+        rng[k].s = w;
+    }
+    auto next_fr = [&](uint8_t* out) {
+        for (;;) {
+            uint64_t c[4] = {rng[0].next(), rng[1].next(), rng[2].next(), rng[3].next() & 0x3FFFFFFFFFFFFFFFULL};
+            if (!HFr::geq_p(c)) {
+                memcpy(out, c, 32);
+                return;
+            }
+        }
+    };
+    const uint64_t n = 1ull << nv;
+    std::vector<uint8_t> table(32 * n), point(32 * nv);
+    for (int i = 0; i < nv; ++i) next_fr(point.data() + 32 * i);
+    for (uint64_t x = 0; x < n; ++x) next_fr(table.data() + 32 * x);
+    const std::vector<uint8_t> com = k_commit(C, P, table.data(), nv);
+    const std::vector<uint8_t> op = k_open(C, P, table.data(), nv, point.data());
+    const VP V = pp_derive_vp(C, P);
+    r.opening_ok = pc_verify(V, com.data(), point.data(), nv, op.data(), op.data() + 32, op.size() - 32) ? 1 : 0;
+    if (!r.opening_ok) r.message = "opening self-test failed";
+    r.stage_ms[1] = t2.us() / 1000.0;
+    return r;
+}
+
+std::unique_ptr<PP> pp_view(Ctx& C, const PP& parent, int nv) {
+    if (nv < 1 || nv > parent.nv) invalid("view: nv out of range (1 .. the parent's nv)");
+    if (C.device != parent.store->device) invalid("view: the context is on another device than the public parameter");
+    const int k = parent.nv - nv;
+    auto V = std::make_unique<PP>();
+    V->nv = nv;
+    V->store = parent.store;
+    V->raw_base = parent.raw_base + parent.lvl_off[k];
+    V->lvl_off.resize(nv + 1);
+    for (int i = 0; i <= nv; ++i) V->lvl_off[i] = parent.lvl_off[k + i] - parent.lvl_off[k];
+    V->g = parent.g;
+    V->h = parent.h;
+    V->g2_off.assign(parent.g2_off.begin() + k, parent.g2_off.end());
+    V->g2_c.assign(parent.g2_c.begin() + k, parent.g2_c.end());
+    V->g2_W.assign(parent.g2_W.begin() + k, parent.g2_W.end());
+    // the shared levels keep the root's window bits: a batch of them has no more buckets than the root's
+    uint64_t buckets = 0;
+    for (int i = 0; i < nv; ++i) buckets += 1ull << (V->g2_c[i] - 1);
+    if (buckets > kMsmMaxBuckets) invalid("view: the shared levels' buckets exceed the MSM sort's bins");
+    V->has_t = parent.has_t;
+    if (parent.has_t) V->t.assign(parent.t.begin() + k, parent.t.end());
+    V->borrowed = (sizeof(G1Aff) + sizeof(G2Aff)) * V->lvl_off[nv] + sizeof(G2Aff) * (V->g2_off[nv] - V->g2_off[0]);
+    if (k == 0) {
+        V->g1_pre = parent.g1_pre;
+        V->g1_pre_own = false;
+        V->g1_c = parent.g1_c, V->g1_W = parent.g1_W;
+        V->borrowed += parent.g1_pre->bytes;
+    } else {
+        const uint64_t n = 1ull << nv;
+        V->g1_c = window_bits_for(n, msm_wide_min_log());
+        V->g1_W = windows_for(V->g1_c);
+        V->g1_pre = std::make_shared<DevMem>(sizeof(G1Slot) * n * V->g1_W);
+        precompute_level(C, V->g1_level(0), n, false, V->g1_c, V->g1_W, V->g1_pre->as<G1Slot>());
+    }
+    return V;
+}
+
+void pp_mem_info(const PP& P, uint64_t out[3]) {
+    const PPStore& S = *P.store;
+    const uint64_t g1 = P.g1_pre_own ? P.g1_pre->bytes : 0;
+    out[0] = P.borrowed ? g1 : g1 + S.g1_raw_mem.bytes + S.g2_raw_mem.bytes + S.g2_pre.bytes;
+    out[1] = P.borrowed;
+    out[2] = (uint64_t)P.store.use_count();
 }
 
 static HostCsr single(const HostCsr& m) { return m; }

@@ -307,25 +307,45 @@ struct CtxClaim {
 };
 
 // ---------------------------------------------------------------- public parameters
+// The device storage of a loaded or generated public parameter. The handle that allocated it and every
+// view of it (pp_view) hold it jointly; it is released with the last of them.
+struct PPStore {
+    int device = 0;
+    DevMem g1_raw_mem, g2_raw_mem;  // all levels of the root parameter, contiguous
+    DevMem g2_pre;                  // the root's G2 opening tables
+};
 struct PP {
     int nv = 0;
-    DevMem g1_raw_mem, g2_raw_mem;            // all levels, contiguous
-    std::vector<uint64_t> lvl_off;            // point offset of level i (2^(nv-i) points)
+    std::shared_ptr<PPStore> store;
+    uint64_t raw_base = 0;                    // point offset of this parameter's level 0 in the store's raw levels
+    std::vector<uint64_t> lvl_off;            // point offset of level i (2^(nv-i) points) from raw_base
     host::Affine<host::Fq> g;
     host::Affine<host::Fq2> h;
-    // window copies (device, affine): commit bases (level 0 of G1)
-    DevMem g1_pre;
+    // window copies (device, affine): commit bases (level 0 of G1). A view of all the levels shares its
+    // parent's table; every other handle builds its own.
+    std::shared_ptr<DevMem> g1_pre;
+    bool g1_pre_own = true;
     int g1_c = 0, g1_W = 0;
-    // G2 opening bases: level i pair-summed (2^(nv-i-1) points), copies [W_i][size_i]
-    DevMem g2_pre;
+    // G2 opening bases: level i pair-summed (2^(nv-i-1) points), copies [W_i][size_i] at g2_pre() +
+    // g2_off[i] (a view: the root's tables of its levels, with the root's window bits)
     std::vector<uint64_t> g2_off;
     std::vector<int> g2_c, g2_W;
     bool has_t = false;
     std::vector<host::Fr> t;  // trapdoor (keygen only; tests)
-    G1Aff* g1_level(int i) const { return g1_raw_mem.as<G1Aff>() + lvl_off[i]; }
-    G2Aff* g2_level(int i) const { return g2_raw_mem.as<G2Aff>() + lvl_off[i]; }
+    uint64_t borrowed = 0;    // device bytes of a parent's that this handle uses (0: not a view)
+    G1Aff* g1_raw() const { return store->g1_raw_mem.as<G1Aff>() + raw_base; }
+    G2Aff* g2_raw() const { return store->g2_raw_mem.as<G2Aff>() + raw_base; }
+    G1Aff* g1_level(int i) const { return g1_raw() + lvl_off[i]; }
+    G2Aff* g2_level(int i) const { return g2_raw() + lvl_off[i]; }
+    const G1Slot* g1_tab() const { return g1_pre->as<G1Slot>(); }
+    const G2Aff* g2_pre() const { return store->g2_pre.as<G2Aff>(); }
 };
 void pp_preprocess(Ctx& C, PP& P);
+// The parameter of nv variables inside `parent` (levels parent.nv - nv .. of both curves, g, h): borrows the
+// root's raw levels and G2 tables, builds only its own G1 commitment table (none when nv == parent.nv).
+std::unique_ptr<PP> pp_view(Ctx& C, const PP& parent, int nv);
+// {device bytes this handle allocated, device bytes it borrows, handles alive on its storage}
+void pp_mem_info(const PP& P, uint64_t out[3]);
 // The MSM window plan (prover.cpp): bits and windows by size, SPX_MSM_WIDE_MIN_LOG, the G2 levels' bits
 int window_bits_for(uint64_t size, int wide_min_log);
 int windows_for(int c);
@@ -459,6 +479,27 @@ struct VP {
 VP vp_load(const uint8_t* b, size_t len);
 std::vector<uint8_t> vp_serialize(const VP& V);
 VP vp_from_pp(const PP& P);  // keygen-generated PP only (keeps the trapdoor)
+// The verifier parameter of any PP: g_mask[i] = the sum of the odd-index points of powers_of_g[i] (= g^{t_i}
+// for a parameter with the structure pp_check_structure tests), summed on the GPU (pp_kernels.hip)
+VP pp_derive_vp(Ctx& C, const PP& P);
+// MLPolyCommit::verify (verify.rs:12-45) on the host: com56 = nv (u64) + compressed G1, proof = compressed
+// h, u64 count, count compressed G2 points. Throws kSerialization / kInvalidArgument for malformed input.
+bool pc_verify(const VP& V, const uint8_t com56[56], const uint8_t* point, int nv, const uint8_t value[32],
+               const uint8_t* proof, size_t proof_len);
+// Structure of a public parameter ("Public-parameter structure and views"). Stage 1: the fold
+// relation of every pair of every level of both curves (bad, first = {curve 1 | 2, level, pair} of the
+// lowest failing pair in the order G1 levels, G2 levels). Stage 2, only when stage 1 passed: a commitment
+// to a pseudo-random table opened at a pseudo-random point verifies under the derived VP (opening_ok 1 |
+// 0; -1: not run).
+struct PPStructureReport {
+    uint64_t bad = 0;
+    uint64_t first[3] = {0, 0, 0};
+    int opening_ok = -1;
+    std::string message;  // empty when the parameter passed
+    double stage_ms[2] = {0, 0};  // host wall time of the stages
+    double fold_kernel_ms = 0;    // device time of stage 1's two k_fold_check launches
+};
+PPStructureReport pp_check_structure(Ctx& C, PP& P, const uint8_t* entropy32);
 // throws SpxError(kInvalidArgument / kSumcheck / kWrongWitness / kSerialization) on rejection, as the
 // reference's Err(...); returns normally on acceptance (Ok(true))
 void verify(Ctx& C, Index& I, const uint8_t* v, size_t nv, const uint8_t* proof, size_t len, const VP& V,
