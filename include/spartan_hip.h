@@ -168,6 +168,41 @@ int spx_pp_free(spx_pp *pp);
 /* ---- index / witness / prove ---- */
 int spx_index(spx_ctx *ctx, const spx_csr *a, const spx_csr *b, const spx_csr *c, spx_pk **out);
 int spx_index_free(spx_pk *idx);
+/* Who builds the device layouts of this context's indices (no effect on the arrays, and so none on any
+ * proof): 0 = the host builder (the default), 1 = the GPU builder: each matrix is uploaded once, its
+ * values converted to Montgomery form once, and HIP kernels make the row layout (CSR block or
+ * column-sorted list), the last-entry-wins CSC and the column stream while the calling thread absorbs
+ * A, B, C into the cached transcript; -1 = the process default (SPX_INDEX_BUILD=gpu -> 1, else 0). The
+ * host-side checks of the matrices, their statuses and messages are the same. The GPU builder takes
+ * fewer than 2^31 entries in A, B and C together (SPX_INVALID_ARGUMENT otherwise). Each rank of a
+ * proof-sharded prove may choose its own. SPX_INVALID_ARGUMENT while the context is in use. */
+int spx_ctx_set_index_build(spx_ctx *ctx, int mode);
+/* Diagnostic: the raw bytes of one device array of an index (values in the device's Montgomery form:
+ * 8 32-bit limbs, least significant first). With out == NULL only *len is written. Lengths are the
+ * logical ones; a part the index does not have (the sliced list of a CSR index and the reverse, the
+ * long tables of an index without long rows or columns) has length 0. Element layouts: PTR uint64,
+ * IDX / COL / DST / LANES / ROWM uint32, VAL 32 B, CHUNKS {u32 m, u32 0, u64 begin, u64 end},
+ * LROWS {u32 m, u32 chunk_begin, u32 chunk_end, u32 0, u64 x}, SLICES {u64 off, u32 len, u32 0}. */
+enum {
+    SPX_IDX_ROWS_PTR_A = 0, SPX_IDX_ROWS_PTR_B, SPX_IDX_ROWS_PTR_C,
+    SPX_IDX_ROWS_IDX_A, SPX_IDX_ROWS_IDX_B, SPX_IDX_ROWS_IDX_C,
+    SPX_IDX_ROWS_VAL_A, SPX_IDX_ROWS_VAL_B, SPX_IDX_ROWS_VAL_C,
+    SPX_IDX_ROWS_CHUNKS, SPX_IDX_ROWS_LROWS,
+    SPX_IDX_SLICED_VAL, SPX_IDX_SLICED_COL, SPX_IDX_SLICED_DST,
+    SPX_IDX_COLS_SLICES, SPX_IDX_COLS_LANES, SPX_IDX_COLS_ROWM, SPX_IDX_COLS_VAL,
+    SPX_IDX_LONGC_IDX_A, SPX_IDX_LONGC_IDX_B, SPX_IDX_LONGC_IDX_C,
+    SPX_IDX_LONGC_VAL_A, SPX_IDX_LONGC_VAL_B, SPX_IDX_LONGC_VAL_C,
+    SPX_IDX_LONGC_CHUNKS, SPX_IDX_LONGC_LROWS,
+    SPX_IDX_PART_COUNT
+};
+int spx_index_export(spx_pk *idx, int part, uint8_t *out, size_t cap, size_t *len);
+/* out[0] the builder that made the index (0 host | 1 GPU), out[1] its row layout (1 = the column-sorted
+ * list, 0 = CSR), out[2] entries of the row layout, out[3] live entries of the local columns (after
+ * last-entry-wins), out[4] long rows (records of more than 64 entries), out[5] local columns of more
+ * than 62 entries, out[6] wall microseconds of the whole spx_index call, out[7] microseconds of it
+ * the calling thread spent absorbing A, B, C into the cached transcript. With the GPU builder,
+ * spx_last_timings[0] after spx_index is the device time (us, HIP events) of its kernels. */
+int spx_index_stats(spx_pk *idx, uint64_t out[8]);
 int spx_witness_upload(spx_ctx *ctx, const uint8_t *v, size_t nv, const uint8_t *w, size_t nw, spx_witness **out);
 int spx_witness_free(spx_witness *wit);
 size_t spx_proof_size(int log_n, int log_v);

@@ -109,6 +109,9 @@ EXPORTED = [
     "spx_pp_free",
     "spx_index",
     "spx_index_free",
+    "spx_ctx_set_index_build",
+    "spx_index_export",
+    "spx_index_stats",
     "spx_witness_upload",
     "spx_witness_free",
     "spx_proof_size",
@@ -233,6 +236,9 @@ def lib():
     L.spx_pp_free.argtypes = [vp]
     L.spx_index.argtypes = [vp, ctypes.POINTER(_CCsr), ctypes.POINTER(_CCsr), ctypes.POINTER(_CCsr), ctypes.POINTER(vp)]
     L.spx_index_free.argtypes = [vp]
+    L.spx_ctx_set_index_build.argtypes = [vp, ctypes.c_int]
+    L.spx_index_export.argtypes = [vp, ctypes.c_int, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
+    L.spx_index_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.spx_witness_upload.argtypes = [vp, u8p, sz, u8p, sz, ctypes.POINTER(vp)]
     L.spx_witness_free.argtypes = [vp]
     L.spx_proof_size.restype = sz
@@ -414,6 +420,12 @@ class Context:
         default), 0 off (listed and counted only: A/B), -1 the process default (SPX_MSM_HOT); no effect
         on the proof bytes (spx_ctx_set_msm_hot)"""
         _check(lib().spx_ctx_set_msm_hot(self.h, int(mode)))
+
+    def set_index_build(self, mode):
+        """who builds the device layouts of this context's indices: 1 = the GPU builder, 0 = the host
+        builder (the default), -1 = the process default (SPX_INDEX_BUILD=gpu -> 1); the arrays, and so
+        every proof, are the same either way (spx_ctx_set_index_build)"""
+        _check(lib().spx_ctx_set_index_build(self.h, int(mode)))
 
     def set_subgroup_check(self, mode):
         """subgroup check of proof points in verify / verify_many on this context: 1 on, 0 off (the
@@ -744,11 +756,42 @@ class PublicParameter:
             pass
 
 
+# parts of an index for IndexPK.export (spartan_hip.h: SPX_IDX_*), in the header's order
+INDEX_PARTS = [
+    "IDX_ROWS_PTR_A", "IDX_ROWS_PTR_B", "IDX_ROWS_PTR_C", "IDX_ROWS_IDX_A", "IDX_ROWS_IDX_B", "IDX_ROWS_IDX_C",
+    "IDX_ROWS_VAL_A", "IDX_ROWS_VAL_B", "IDX_ROWS_VAL_C", "IDX_ROWS_CHUNKS", "IDX_ROWS_LROWS",
+    "IDX_SLICED_VAL", "IDX_SLICED_COL", "IDX_SLICED_DST",
+    "IDX_COLS_SLICES", "IDX_COLS_LANES", "IDX_COLS_ROWM", "IDX_COLS_VAL",
+    "IDX_LONGC_IDX_A", "IDX_LONGC_IDX_B", "IDX_LONGC_IDX_C", "IDX_LONGC_VAL_A", "IDX_LONGC_VAL_B", "IDX_LONGC_VAL_C",
+    "IDX_LONGC_CHUNKS", "IDX_LONGC_LROWS",
+]
+for _i, _name in enumerate(INDEX_PARTS):
+    globals()[_name] = _i
+IDX_PART_COUNT = len(INDEX_PARTS)
+INDEX_STATS = ["builder", "sliced", "row_entries", "col_entries", "long_rows", "long_cols", "wall_us", "absorb_us"]
+
+
 class IndexPK:
     """ahp/indexer.rs:9-17 (prover key)."""
 
     def __init__(self, ctx, h, log_n):
         self.ctx, self.h, self.log_n = ctx, h, log_n
+
+    def export(self, part):
+        """diagnostic: the raw bytes of device array `part` (IDX_*) of the index, values in the device's
+        Montgomery form; empty for a part the index does not have (spx_index_export)"""
+        n = ctypes.c_size_t(0)
+        _check(lib().spx_index_export(self.h, int(part), None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(max(n.value, 1))
+        _check(lib().spx_index_export(self.h, int(part), buf, n.value, ctypes.byref(n)))
+        return buf.raw[: n.value]
+
+    def stats(self):
+        """[builder (0 host | 1 GPU), sliced rows (0 | 1), row entries, live column entries, long rows, long
+        columns, wall us of the spx_index call, us of it absorbing A, B, C] (spx_index_stats; INDEX_STATS)"""
+        out = (ctypes.c_uint64 * 8)()
+        _check(lib().spx_index_stats(self.h, out))
+        return list(out)
 
     def __del__(self):
         try:

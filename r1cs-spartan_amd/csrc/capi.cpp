@@ -341,8 +341,40 @@ int spx_pp_free(spx_pp* pp) {
 int spx_index(spx_ctx* ctx, const spx_csr* a, const spx_csr* b, const spx_csr* c, spx_pk** out) {
     return guard([&] {
         set_dev(ctx);
+        const auto t0 = std::chrono::steady_clock::now();
         spx::HostCsr m[3] = {to_host(a), to_host(b), to_host(c)};
-        *out = new spx_pk{ctx, spx::index_build(*ctx->c, m)};
+        auto I = spx::index_build(*ctx->c, m);
+        I->build_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        *out = new spx_pk{ctx, std::move(I)};
+    });
+}
+int spx_ctx_set_index_build(spx_ctx* ctx, int mode) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (mode < -1 || mode > 1) spx::invalid("index build mode must be -1, 0 or 1");
+        if (ctx->c->in_use.load()) spx::invalid("context in use by a prove or session");
+        ctx->c->index_mode = mode;
+    });
+}
+int spx_index_export(spx_pk* idx, int part, uint8_t* out, size_t cap, size_t* len) {
+    return guard([&] {
+        if (!idx) spx::invalid("null prover key");
+        set_dev(idx->ctx);
+        copy_out(spx::index_export(*idx->i, part), out, cap, len);
+    });
+}
+int spx_index_stats(spx_pk* idx, uint64_t out[8]) {
+    return guard([&] {
+        if (!idx || !out) spx::invalid("null argument");
+        const spx::Index& I = *idx->i;
+        out[0] = (uint64_t)I.builder;
+        out[1] = I.rows_sliced.on ? 1 : 0;
+        out[2] = I.row_entries;
+        out[3] = I.cols.entries;
+        out[4] = (uint64_t)I.rows.nlrows;
+        out[5] = I.long_cols;
+        out[6] = (uint64_t)I.build_us;
+        out[7] = (uint64_t)I.absorb_us;
     });
 }
 int spx_index_free(spx_pk* idx) {

@@ -181,6 +181,51 @@ inline void kp_end(double bytes, hipStream_t s, double ops = 0) {
 enum { KP_SC1 = 0, KP_SC2, KP_SPMV, KP_MTV, KP_OPEN, KP_EQ, KP_SORT, KP_ACC_G1, KP_ACC_G2, KP_ACCX_G1, KP_ACCX_G2,
        KP_RED_G1, KP_RED_G2 };
 
+// ---- index_kernels.hip: the index's device layouts built from the uploaded host CSR (index_build_gpu)
+struct IndexSrc {           // A, B, C as uploaded: entries concatenated in that order
+    const uint64_t* rp[3];  // [n + 1] row pointers of each matrix
+    uint64_t base[4];       // first concatenated entry of matrix m; base[3] = all entries (< 2^31)
+    const uint32_t* col;    // [base[3]]
+    const Fr* val;          // [base[3]] Montgomery
+    uint64_t n;
+};
+struct IndexLongOut {  // DevColStream::longc's per-matrix entry arrays
+    uint32_t* idx[3];
+    Fr* val[3];
+};
+// exclusive scan of n 32-bit words in place; sums: index_scan_scratch(n) words
+uint64_t index_scan_scratch(uint64_t n);
+void launch_index_scan(uint32_t* d, uint64_t n, uint32_t* sums, hipStream_t s);
+// stable sort of E (key, payload) pairs by the low `bits` bits of the key, ping-pong between the two
+// buffer pairs; returns the pair that holds the result (0: key / pay, 1: key2 / pay2). hist:
+// index_sort_hist_words(E) words, sums: index_scan_scratch(that)
+uint64_t index_sort_hist_words(uint64_t E);
+int launch_index_sort(uint32_t* key, uint32_t* pay, uint32_t* key2, uint32_t* pay2, uint64_t E, int bits, uint32_t* hist,
+                      uint32_t* sums, hipStream_t s);
+void launch_index_iota(uint32_t* d, uint64_t n, hipStream_t s);
+void launch_index_rebase(const uint64_t* rp, uint64_t lo, uint64_t nl, uint64_t* ptr, hipStream_t s);
+// the sliced list of rows [lo, lo + nl): 3 nl (column, m nl + row - lo) pairs to sort by column, then the list
+void launch_index_sliced_keys(const IndexSrc& src, uint64_t lo, uint64_t nl, uint32_t* key, uint32_t* pay, hipStream_t s);
+void launch_index_sliced_fill(const IndexSrc& src, uint64_t lo, uint64_t nl, const uint32_t* key, const uint32_t* pay,
+                              Fr* val, uint32_t* col, uint32_t* dst, hipStream_t s);
+// CSC of the three matrices from the column-sorted (column, concatenated entry) pairs: row | m << 30 of
+// every entry, last-entry-wins, compaction (ckey, crowm, cpay: the live entries; pos[E] = their number;
+// pos: E + 1 words, sums: index_scan_scratch(E + 1))
+void launch_index_csc(const IndexSrc& src, const uint32_t* key, const uint32_t* pay, uint64_t E, uint32_t* rowm,
+                      uint32_t* pos, uint32_t* sums, uint32_t* ckey, uint32_t* crowm, uint32_t* cpay, hipStream_t s);
+// cpl[3 y + m], y in [0, nl): first live entry of (column lo + y, matrix m); cpl[3 nl] closes the last
+void launch_index_col_ptr(const uint32_t* ckey, const uint32_t* crowm, const uint32_t* nlive, uint64_t lo, uint64_t nl,
+                          uint32_t* cpl, hipStream_t s);
+// lanes ([64 nslices], preset to kColNone) and every slice's length; *nlong += columns longer than kLongCol
+void launch_index_col_window(const uint32_t* cpl, uint64_t nl, uint32_t* lanes, uint32_t* slice_len, uint32_t* nlong,
+                             hipStream_t s);
+void launch_index_stream_fill(const ColSlice* slices, const uint32_t* lanes, uint64_t nslices, const uint32_t* cpl,
+                              const uint32_t* crowm, const uint32_t* cpay, const Fr* src_val, uint32_t* rowm, Fr* val,
+                              hipStream_t s);
+void launch_index_long_fill(const LongRow* lrows, int nlrows, const LongChunk* chunks, const uint32_t* cpl,
+                            const uint32_t* crowm, const uint32_t* cpay, const Fr* src_val, const IndexLongOut& out,
+                            hipStream_t s);
+
 // ---- mle_kernels.hip
 void launch_to_mont(Fr* d, size_t n, int* err, hipStream_t s);
 void launch_from_mont(Fr* out, const Fr* in, size_t n, hipStream_t s);

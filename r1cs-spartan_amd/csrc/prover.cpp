@@ -758,6 +758,241 @@ void absorb_matrices_lanes(const Index& I, Blake2s* out, int k) {
     for (int m = 0; m < 3; ++m) feed_matrix(sink, I.m[m]);
 }
 
+bool index_gpu_default() {  // SPX_INDEX_BUILD=gpu: contexts build their indices on the GPU unless told otherwise
+    const char* e = getenv("SPX_INDEX_BUILD");
+    return e && !strcmp(e, "gpu");
+}
+bool Ctx::index_gpu() const { return index_mode < 0 ? index_gpu_default() : index_mode == 1; }
+
+namespace {
+struct EventPair {  // device time of a stretch of the stream
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() {
+        SPX_HIP(hipEventCreate(&a));
+        SPX_HIP(hipEventCreate(&b));
+    }
+    ~EventPair() {
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+    }
+    double ms() const {
+        float t = 0;
+        SPX_HIP(hipEventElapsedTime(&t, a, b));
+        return t;
+    }
+};
+double us_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+
+// The GPU builder ("Index build on the GPU"): the arrays upload_sliced / upload_sparse,
+// build_csc and upload_cols make, byte for byte, from one upload of each matrix (row_ptr, col, val; the
+// values converted to Montgomery form once) and the kernels of index_kernels.hip. The calling thread
+// absorbs A while the sorts run, waits for the slice lengths (the stream's size), queues the fills and
+// absorbs B and C beside them. Every host source of a copy (the caller's matrices, the tables below)
+// lives until the last sync; the scratch is freed on return.
+static void index_build_gpu(Ctx& C, Index& I, const HostCsr* mats, uint64_t n, uint64_t lo, uint64_t nl, int* err_dev) {
+    hipStream_t s = C.stream;
+    uint64_t base[4] = {0, 0, 0, 0};
+    for (int m = 0; m < 3; ++m) base[m + 1] = base[m] + mats[m].rp[n];
+    const uint64_t E = base[3];
+    if (E >= (1ull << 31)) invalid("the GPU index builder takes fewer than 2^31 matrix entries in all");
+    // ---- the one upload
+    DevMem rp[3], col(4 * std::max<uint64_t>(E, 1)), val(32 * std::max<uint64_t>(E, 1));
+    for (int m = 0; m < 3; ++m) {
+        rp[m].alloc(8 * (n + 1));
+        SPX_HIP(hipMemcpyAsync(rp[m].p, mats[m].rp.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+        const uint64_t nnz = base[m + 1] - base[m];
+        if (!nnz) continue;
+        SPX_HIP(hipMemcpyAsync(col.as<uint32_t>() + base[m], mats[m].col.data(), 4 * nnz, hipMemcpyHostToDevice, s));
+        SPX_HIP(hipMemcpyAsync(val.as<uint8_t>() + 32 * base[m], mats[m].val.data(), 32 * nnz, hipMemcpyHostToDevice, s));
+    }
+    EventPair ev1, ev2;
+    SPX_HIP(hipEventRecord(ev1.a, s));
+    launch_to_mont(val.as<Fr>(), E, err_dev, s);
+    IndexSrc src{};
+    for (int m = 0; m < 3; ++m) src.rp[m] = rp[m].as<uint64_t>();
+    for (int m = 0; m < 4; ++m) src.base[m] = base[m];
+    src.col = col.as<uint32_t>();
+    src.val = val.as<Fr>();
+    src.n = n;
+    bool sliced = n >= (1ull << 12);
+    for (int m = 0; m < 3 && sliced; ++m)
+        for (uint64_t x = lo; x < lo + nl; ++x)
+            if (mats[m].rp[x + 1] - mats[m].rp[x] > 1) {
+                sliced = false;
+                break;
+            }
+    // ---- scratch of both sorts and of the CSC
+    const uint64_t Es = std::max<uint64_t>(std::max<uint64_t>(E, sliced ? 3 * nl : 0), 1);
+    const uint64_t hw = std::max<uint64_t>(index_sort_hist_words(Es), 1);
+    DevMem k1(4 * Es), p1(4 * Es), k2(4 * Es), p2(4 * Es), hist(4 * hw);
+    DevMem sums(4 * index_scan_scratch(std::max(hw, E + 1)));
+    std::vector<LongChunk> chunks;  // rows' long tables (CSR path)
+    std::vector<LongRow> lrows;
+    if (sliced) {
+        DevSliced& S = I.rows_sliced;
+        const uint64_t Er = 3 * nl;
+        launch_index_sliced_keys(src, lo, nl, k1.as<uint32_t>(), p1.as<uint32_t>(), s);
+        const int side = launch_index_sort(k1.as<uint32_t>(), p1.as<uint32_t>(), k2.as<uint32_t>(), p2.as<uint32_t>(), Er,
+                                           I.log_n, hist.as<uint32_t>(), sums.as<uint32_t>(), s);
+        S.val.alloc(32 * Er);
+        S.col.alloc(4 * Er);
+        S.dst.alloc(4 * Er);
+        launch_index_sliced_fill(src, lo, nl, (side ? k2 : k1).as<uint32_t>(), (side ? p2 : p1).as<uint32_t>(),
+                                 S.val.as<Fr>(), S.col.as<uint32_t>(), S.dst.as<uint32_t>(), s);
+        S.entries = Er;
+        S.on = true;
+    } else {
+        DevSparse& D = I.rows;
+        for (int m = 0; m < 3; ++m) {
+            const std::vector<uint64_t>& r = mats[m].rp;
+            const uint64_t b0 = r[lo], nnz = r[lo + nl] - b0;
+            D.ptr[m].alloc(8 * (nl + 1));
+            D.idx[m].alloc(4 * std::max<uint64_t>(nnz, 1));
+            D.val[m].alloc(32 * std::max<uint64_t>(nnz, 1));
+            launch_index_rebase(src.rp[m], lo, nl, D.ptr[m].as<uint64_t>(), s);
+            if (nnz) {
+                SPX_HIP(hipMemcpyAsync(D.idx[m].p, src.col + base[m] + b0, 4 * nnz, hipMemcpyDeviceToDevice, s));
+                SPX_HIP(hipMemcpyAsync(D.val[m].p, src.val + base[m] + b0, 32 * nnz, hipMemcpyDeviceToDevice, s));
+            }
+            for (uint64_t x = 0; x < nl; ++x) {
+                const uint64_t b = r[lo + x] - b0, e = r[lo + x + 1] - b0;
+                if (e - b <= kLongRow) continue;
+                LongRow lr{};
+                lr.m = (uint32_t)m;
+                lr.x = x;
+                lr.chunk_begin = (uint32_t)chunks.size();
+                for (uint64_t k = b; k < e; k += kChunk) {
+                    LongChunk ch{};
+                    ch.m = (uint32_t)m;
+                    ch.begin = k;
+                    ch.end = std::min(k + kChunk, e);
+                    chunks.push_back(ch);
+                }
+                lr.chunk_end = (uint32_t)chunks.size();
+                lrows.push_back(lr);
+            }
+        }
+        D.nchunks = (int)chunks.size();
+        D.nlrows = (int)lrows.size();
+        if (D.nchunks) {
+            D.chunks.alloc(sizeof(LongChunk) * chunks.size());
+            D.lrows.alloc(sizeof(LongRow) * lrows.size());
+            SPX_HIP(hipMemcpyAsync(D.chunks.p, chunks.data(), sizeof(LongChunk) * chunks.size(), hipMemcpyHostToDevice, s));
+            SPX_HIP(hipMemcpyAsync(D.lrows.p, lrows.data(), sizeof(LongRow) * lrows.size(), hipMemcpyHostToDevice, s));
+        }
+    }
+    // ---- CSC of the whole matrices: entries sorted by column (stable: A, B, C, rows ascending, a row's
+    // entries in their order), the superseded ones dropped, then the local columns' pointers
+    if (E) SPX_HIP(hipMemcpyAsync(k1.p, col.p, 4 * E, hipMemcpyDeviceToDevice, s));
+    launch_index_iota(p1.as<uint32_t>(), E, s);
+    const int side = launch_index_sort(k1.as<uint32_t>(), p1.as<uint32_t>(), k2.as<uint32_t>(), p2.as<uint32_t>(), E,
+                                       I.log_n, hist.as<uint32_t>(), sums.as<uint32_t>(), s);
+    const uint32_t *skey = (side ? k2 : k1).as<uint32_t>(), *spay = (side ? p2 : p1).as<uint32_t>();
+    uint32_t *ckey = (side ? k1 : k2).as<uint32_t>(), *cpay = (side ? p1 : p2).as<uint32_t>();
+    DevMem rowm(4 * std::max<uint64_t>(E, 1)), crowm(4 * std::max<uint64_t>(E, 1)), pos(4 * (E + 1)), cpl(4 * (3 * nl + 1));
+    launch_index_csc(src, skey, spay, E, rowm.as<uint32_t>(), pos.as<uint32_t>(), sums.as<uint32_t>(), ckey,
+                     crowm.as<uint32_t>(), cpay, s);
+    launch_index_col_ptr(ckey, crowm.as<uint32_t>(), pos.as<uint32_t>() + E, lo, nl, cpl.as<uint32_t>(), s);
+    // ---- column stream: the windows' lane words and slice lengths, then (sizes known) the entry slots
+    DevColStream& D = I.cols;
+    const uint64_t nslices = (nl + 63) / 64;
+    D.nslices = (uint32_t)nslices;
+    D.slices.alloc(sizeof(ColSlice) * nslices);
+    D.lanes.alloc(4 * 64 * nslices);
+    DevMem slen(4 * nslices), nlong_dev(4);
+    SPX_HIP(hipMemsetAsync(D.lanes.p, 0xFF, 4 * 64 * nslices, s));
+    SPX_HIP(hipMemsetAsync(nlong_dev.p, 0, 4, s));
+    launch_index_col_window(cpl.as<uint32_t>(), nl, D.lanes.as<uint32_t>(), slen.as<uint32_t>(), nlong_dev.as<uint32_t>(), s);
+    SPX_HIP(hipEventRecord(ev1.b, s));
+    std::vector<uint32_t> h_slen(nslices), h_cpl;
+    uint32_t h_nlong = 0, h_cp[2] = {0, 0};
+    SPX_HIP(hipMemcpyAsync(h_slen.data(), slen.p, 4 * nslices, hipMemcpyDeviceToHost, s));
+    SPX_HIP(hipMemcpyAsync(&h_nlong, nlong_dev.p, 4, hipMemcpyDeviceToHost, s));
+    SPX_HIP(hipMemcpyAsync(&h_cp[0], cpl.p, 4, hipMemcpyDeviceToHost, s));
+    SPX_HIP(hipMemcpyAsync(&h_cp[1], cpl.as<uint32_t>() + 3 * nl, 4, hipMemcpyDeviceToHost, s));
+    auto t0 = std::chrono::steady_clock::now();
+    feed_matrix(I.cache, mats[0]);
+    I.absorb_us += us_since(t0);
+    C.sync();
+    if (h_nlong) {  // long columns are rare: only then do the local column pointers come back
+        h_cpl.resize(3 * nl + 1);
+        SPX_HIP(hipMemcpyAsync(h_cpl.data(), cpl.p, 4 * (3 * nl + 1), hipMemcpyDeviceToHost, s));
+        C.sync();
+    }
+    D.entries = h_cp[1] - h_cp[0];
+    I.long_cols = h_nlong;
+    std::vector<ColSlice> sl(nslices);
+    uint64_t tot = 0;
+    for (uint64_t si = 0; si < nslices; ++si) {
+        sl[si].off = tot;
+        sl[si].len = h_slen[si];
+        sl[si].pad = 0;
+        tot += 64ull * h_slen[si];
+    }
+    D.rowm.alloc(4 * std::max<uint64_t>(tot, 1));
+    D.val.alloc(32 * std::max<uint64_t>(tot, 1));
+    SPX_HIP(hipEventRecord(ev2.a, s));
+    SPX_HIP(hipMemcpyAsync(D.slices.p, sl.data(), sizeof(ColSlice) * nslices, hipMemcpyHostToDevice, s));
+    SPX_HIP(hipMemsetAsync(D.rowm.p, 0, D.rowm.bytes, s));
+    SPX_HIP(hipMemsetAsync(D.val.p, 0, D.val.bytes, s));
+    launch_index_stream_fill(D.slices.as<ColSlice>(), D.lanes.as<uint32_t>(), nslices, cpl.as<uint32_t>(),
+                             crowm.as<uint32_t>(), cpay, src.val, D.rowm.as<uint32_t>(), D.val.as<Fr>(), s);
+    // long columns: per-matrix entry arrays holding only their entries, chunked (as upload_cols)
+    std::vector<LongChunk> lchunks;
+    std::vector<LongRow> llrows;
+    uint64_t lcount[3] = {0, 0, 0};
+    if (h_nlong)
+        for (uint32_t m = 0; m < 3; ++m)
+            for (uint64_t y = 0; y < nl; ++y) {
+                if (h_cpl[3 * y + 3] - h_cpl[3 * y] <= kLongCol) continue;
+                const uint64_t cnt = h_cpl[3 * y + m + 1] - h_cpl[3 * y + m];
+                if (!cnt) continue;
+                LongRow lr{};
+                lr.m = m;
+                lr.x = y;
+                lr.chunk_begin = (uint32_t)lchunks.size();
+                for (uint64_t k = 0; k < cnt; k += kChunk) {
+                    LongChunk ch{};
+                    ch.m = m;
+                    ch.begin = lcount[m] + k;
+                    ch.end = lcount[m] + std::min<uint64_t>(k + kChunk, cnt);
+                    lchunks.push_back(ch);
+                }
+                lr.chunk_end = (uint32_t)lchunks.size();
+                llrows.push_back(lr);
+                lcount[m] += cnt;
+            }
+    DevSparse& L = D.longc;
+    IndexLongOut lout{};
+    for (int m = 0; m < 3; ++m) {
+        L.ptr[m].alloc(8);
+        L.idx[m].alloc(4 * std::max<uint64_t>(lcount[m], 1));
+        L.val[m].alloc(32 * std::max<uint64_t>(lcount[m], 1));
+        lout.idx[m] = L.idx[m].as<uint32_t>();
+        lout.val[m] = L.val[m].as<Fr>();
+    }
+    L.nchunks = (int)lchunks.size();
+    L.nlrows = (int)llrows.size();
+    if (L.nchunks) {
+        L.chunks.alloc(sizeof(LongChunk) * lchunks.size());
+        L.lrows.alloc(sizeof(LongRow) * llrows.size());
+        SPX_HIP(hipMemcpyAsync(L.chunks.p, lchunks.data(), sizeof(LongChunk) * lchunks.size(), hipMemcpyHostToDevice, s));
+        SPX_HIP(hipMemcpyAsync(L.lrows.p, llrows.data(), sizeof(LongRow) * llrows.size(), hipMemcpyHostToDevice, s));
+        launch_index_long_fill(L.lrows.as<LongRow>(), L.nlrows, L.chunks.as<LongChunk>(), cpl.as<uint32_t>(),
+                               crowm.as<uint32_t>(), cpay, src.val, lout, s);
+    }
+    SPX_HIP(hipEventRecord(ev2.b, s));
+    t0 = std::chrono::steady_clock::now();
+    feed_matrix(I.cache, mats[1]);
+    feed_matrix(I.cache, mats[2]);
+    I.absorb_us += us_since(t0);
+    C.sync();
+    I.build_kernel_us = 1000.0 * (ev1.ms() + ev2.ms());
+}
+
 std::unique_ptr<Index> index_build(Ctx& C, const HostCsr* mats) {
     auto I = std::make_unique<Index>();
     const uint64_t n = mats[0].n;
@@ -775,25 +1010,37 @@ std::unique_ptr<Index> index_build(Ctx& C, const HostCsr* mats) {
     const uint64_t nl = n / G, lo = (uint64_t)rank * nl;
     DevMem err(sizeof(int));
     SPX_HIP(hipMemsetAsync(err.p, 0, sizeof(int), C.stream));
-    // rows (CSR) for sum_over_y
-    std::vector<uint64_t> rps[3];
-    std::vector<uint32_t> cols[3];
-    std::vector<uint8_t> vals[3];
-    for (int m = 0; m < 3; ++m) rps[m] = mats[m].rp;
-    if (!upload_sliced(C, I->rows_sliced, mats, n, lo, nl, err.as<int>())) {
-        const std::vector<uint32_t>* ci[3] = {&mats[0].col, &mats[1].col, &mats[2].col};
-        const std::vector<uint8_t>* vi[3] = {&mats[0].val, &mats[1].val, &mats[2].val};
-        std::vector<uint32_t> c3[3];
-        std::vector<uint8_t> v3[3];
-        for (int m = 0; m < 3; ++m) c3[m] = *ci[m], v3[m] = *vi[m];
-        upload_sparse(C, I->rows, rps, c3, v3, lo, nl, err.as<int>());
+    const bool gpu = C.index_gpu();
+    I->builder = gpu ? 1 : 0;
+    if (gpu) {
+        index_build_gpu(C, *I, mats, n, lo, nl, err.as<int>());
+    } else {
+        // rows (CSR) for sum_over_y
+        std::vector<uint64_t> rps[3];
+        std::vector<uint32_t> cols[3];
+        std::vector<uint8_t> vals[3];
+        for (int m = 0; m < 3; ++m) rps[m] = mats[m].rp;
+        if (!upload_sliced(C, I->rows_sliced, mats, n, lo, nl, err.as<int>())) {
+            const std::vector<uint32_t>* ci[3] = {&mats[0].col, &mats[1].col, &mats[2].col};
+            const std::vector<uint8_t>* vi[3] = {&mats[0].val, &mats[1].val, &mats[2].val};
+            std::vector<uint32_t> c3[3];
+            std::vector<uint8_t> v3[3];
+            for (int m = 0; m < 3; ++m) c3[m] = *ci[m], v3[m] = *vi[m];
+            upload_sparse(C, I->rows, rps, c3, v3, lo, nl, err.as<int>());
+        }
+        // columns (CSC, last entry of a repeated (x, y) kept) for eval_on_x
+        for (int m = 0; m < 3; ++m) build_csc(mats[m], n, rps[m], cols[m], vals[m]);
+        upload_cols(C, I->cols, rps, cols, vals, lo, nl, err.as<int>());
+        for (uint64_t y = 0; y < nl; ++y) {  // spx_index_stats: columns on the long path
+            uint64_t L = 0;
+            for (int m = 0; m < 3; ++m) L += rps[m][lo + y + 1] - rps[m][lo + y];
+            I->long_cols += L > kLongCol;
+        }
     }
-    // columns (CSC, last entry of a repeated (x, y) kept) for eval_on_x
-    for (int m = 0; m < 3; ++m) build_csc(mats[m], n, rps[m], cols[m], vals[m]);
-    upload_cols(C, I->cols, rps, cols, vals, lo, nl, err.as<int>());
     {
         double e_rows = 0;
         for (int m = 0; m < 3; ++m) e_rows += (double)(mats[m].rp[lo + nl] - mats[m].rp[lo]);
+        I->row_entries = I->rows_sliced.on ? I->rows_sliced.entries : (uint64_t)e_rows;
         if (I->rows_sliced.on) {
             // column-sorted list: 40 B per entry (value, column, row | matrix), z read once (each XCD
             // its contiguous eighth), one 32 B output per local row and matrix
@@ -811,10 +1058,69 @@ std::unique_ptr<Index> index_build(Ctx& C, const HostCsr* mats) {
     SPX_HIP(hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, C.stream));
     C.sync();
     if (herr) throw SpxError(kSerialization, "non-canonical field element in matrix");
-    // witness-independent transcript prefix (lib.rs:61-64), absorbed once
-    for (int m = 0; m < 3; ++m) feed_matrix(I->cache, mats[m]);
+    // witness-independent transcript prefix (lib.rs:61-64), absorbed once (the GPU builder did, beside its kernels)
+    if (!gpu) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int m = 0; m < 3; ++m) feed_matrix(I->cache, mats[m]);
+        I->absorb_us = us_since(t0);
+    } else {
+        C.timings.clear();
+        C.timings.emplace_back("index_gpu_kernels", I->build_kernel_us);
+    }
     I->has_cache = true;
     return I;
+}
+
+std::vector<uint8_t> index_export(const Index& I, int part) {
+    enum { kPtr = 0, kIdx = 3, kVal = 6, kChunks = 9, kLrows, kSVal, kSCol, kSDst, kSlices, kLanes, kRowm, kCVal,
+           kLIdx = 18, kLVal = 21, kLChunks = 24, kLLrows, kCount };
+    if (part < 0 || part >= kCount) invalid("no such index part");
+    const uint64_t nl = I.n / I.G, lo = (uint64_t)I.rank * nl;
+    auto fetch = [](const DevMem& d, uint64_t bytes) {
+        std::vector<uint8_t> out(bytes);
+        if (bytes) SPX_HIP(hipMemcpy(out.data(), d.p, bytes, hipMemcpyDeviceToHost));
+        return out;
+    };
+    auto chunks_of = [&](const DevSparse& D) {
+        std::vector<LongChunk> ch(D.nchunks);
+        if (D.nchunks) SPX_HIP(hipMemcpy(ch.data(), D.chunks.p, sizeof(LongChunk) * ch.size(), hipMemcpyDeviceToHost));
+        return ch;
+    };
+    const bool csr = I.rows.ptr[0].p != nullptr;
+    if (part < kChunks) {
+        const int m = part % 3;
+        const uint64_t nnz = I.m[m].rp[lo + nl] - I.m[m].rp[lo];
+        if (!csr) return {};
+        if (part < kIdx) return fetch(I.rows.ptr[m], 8 * (nl + 1));
+        return part < kVal ? fetch(I.rows.idx[m], 4 * nnz) : fetch(I.rows.val[m], 32 * nnz);
+    }
+    switch (part) {
+        case kChunks: return fetch(I.rows.chunks, sizeof(LongChunk) * (uint64_t)I.rows.nchunks);
+        case kLrows: return fetch(I.rows.lrows, sizeof(LongRow) * (uint64_t)I.rows.nlrows);
+        case kSVal: return fetch(I.rows_sliced.val, I.rows_sliced.on ? 32 * I.rows_sliced.entries : 0);
+        case kSCol: return fetch(I.rows_sliced.col, I.rows_sliced.on ? 4 * I.rows_sliced.entries : 0);
+        case kSDst: return fetch(I.rows_sliced.dst, I.rows_sliced.on ? 4 * I.rows_sliced.entries : 0);
+        case kSlices: return fetch(I.cols.slices, sizeof(ColSlice) * (uint64_t)I.cols.nslices);
+        case kLanes: return fetch(I.cols.lanes, 4 * 64 * (uint64_t)I.cols.nslices);
+        case kRowm:
+        case kCVal: {  // entry slots: up to the end of the last slice
+            uint64_t tot = 0;
+            if (I.cols.nslices) {
+                ColSlice last{};
+                SPX_HIP(hipMemcpy(&last, I.cols.slices.as<ColSlice>() + (I.cols.nslices - 1), sizeof last, hipMemcpyDeviceToHost));
+                tot = last.off + 64ull * last.len;
+            }
+            return part == kRowm ? fetch(I.cols.rowm, 4 * tot) : fetch(I.cols.val, 32 * tot);
+        }
+        case kLChunks: return fetch(I.cols.longc.chunks, sizeof(LongChunk) * (uint64_t)I.cols.longc.nchunks);
+        case kLLrows: return fetch(I.cols.longc.lrows, sizeof(LongRow) * (uint64_t)I.cols.longc.nlrows);
+        default: break;
+    }
+    const uint32_t m = (uint32_t)(part - kLIdx) % 3;  // a matrix's long-column entries end with its last chunk
+    uint64_t cnt = 0;
+    for (const LongChunk& ch : chunks_of(I.cols.longc))
+        if (ch.m == m) cnt = std::max(cnt, ch.end);
+    return part < kLVal ? fetch(I.cols.longc.idx[m], 4 * cnt) : fetch(I.cols.longc.val[m], 32 * cnt);
 }
 
 std::unique_ptr<Witness> witness_upload(Ctx& C, const uint8_t* v, size_t nv, const uint8_t* w, size_t nw) {

@@ -255,6 +255,11 @@ struct Ctx {
     // clears knobs_agreed). Counters, cumulative: witnesses checked, witnesses rejected, check launches,
     // rows checked (local rows, summed over the launches' proofs)
     int witness_check_mode = -1;
+    // who builds the device layouts of an index (index_build): 1 the kernels of index_kernels.hip, 0 the
+    // host builder, -1 the process default (SPX_INDEX_BUILD=gpu -> 1, else 0). The arrays are equal
+    // either way, so the ranks of a communicator may differ.
+    int index_mode = -1;
+    bool index_gpu() const;
     bool witness_check() const;
     std::atomic<uint64_t> wcstat[4] = {};
     Ctx(int dev);
@@ -405,6 +410,12 @@ struct Index {
     double rows_bytes = 0, cols_bytes = 0;  // algorithmic bytes of one SpMV / eval_on_x pass (local)
     double rows_index_bytes = 0;            // of rows_bytes: the index stream (shared by a lockstep group)
     int G = 1, rank = 0;
+    // spx_index_stats: the builder that made the device arrays (0 host, 1 GPU), entries of the row layout,
+    // local columns on the long path, host wall time of the transcript absorption and of the whole call,
+    // device time of the GPU builder's kernels (events; 0 for the host builder)
+    int builder = 0;
+    uint64_t row_entries = 0, long_cols = 0;
+    double absorb_us = 0, build_us = 0, build_kernel_us = 0;
 };
 
 struct Witness {
@@ -443,6 +454,9 @@ std::unique_ptr<PP> pp_load(Ctx& C, const uint8_t* b, size_t len);
 std::unique_ptr<PP> pp_generate(Ctx& C, int nv, uint64_t seed);
 std::vector<uint8_t> pp_serialize(Ctx& C, const PP& P);
 std::unique_ptr<Index> index_build(Ctx& C, const HostCsr* mats);
+// diagnostic (spx_index_export): the raw bytes of device array `part` (spartan_hip.h: SPX_IDX_*) of an index,
+// logical length (empty for a part the index does not have)
+std::vector<uint8_t> index_export(const Index& I, int part);
 std::unique_ptr<Witness> witness_upload(Ctx& C, const uint8_t* v, size_t nv, const uint8_t* w, size_t nw);
 // P may be null only when o.stub
 std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts& o);
