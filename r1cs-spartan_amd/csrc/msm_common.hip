@@ -679,7 +679,10 @@ MsmPlan msm_plan(const MsmInst* ih, int ninst, const MsmShard& sh, double cap_sc
             acc += nout;
         }
         o.wp[(size_t)lv * (nact + 1) + nact] = acc;
-        if (lv >= 1 && o.top_from > o.levels && std::max(1u, maxc >> (lv - 1)) <= kTopNodes) o.top_from = lv;
+        // k_tree_top from the first level whose input (n nodes, lv - 1 sums U_l begun) fits its LDS
+        const uint32_t n = std::max(1u, maxc >> std::max(lv - 1, 0));
+        if (lv >= 1 && o.top_from > o.levels && n <= kTopNodes && n + (uint64_t)lv * std::max(1u, n / 2) <= kTopElems)
+            o.top_from = lv;
     }
     return o;
 }

@@ -22,6 +22,9 @@ static constexpr uint32_t kTreeChunkLog = 2;
 // k_tree_top: the levels whose input has <= 32 nodes, one launch (one level launch fewer per batch
 // than 16: G = 8 rank +1.0%, N = 1 +1.4%; 64: +0.8% / +0.4%, 147 KB of LDS; profiles/r05/r05zz_ab_topnodes_*.jsonl)
 static constexpr uint32_t kTopNodes = 32;
+// k_tree_top's LDS in XYZZ points (72 KB in G2): at hand-over after level R0 with n nodes it holds
+// the S array (n) and the first halving (n / 2 each) of F and of the R0 sums U_l begun below it
+static constexpr uint32_t kTopElems = 192;
 static constexpr int kLight = 256;  // threads for bookkeeping kernels
 static constexpr int kHeavy = 64;   // threads for curve kernels (register-heavy)
 
@@ -110,7 +113,7 @@ struct PinArena {
 };
 
 struct MsmWorkspace {
-    DBuf tables, offs, refs, pa, pb, tree_a, tree_b;
+    DBuf tables, offs, refs, pa, pb, tree_a;
     // bucket sort (msm_sort): per-(bin, tile) counts and their row prefixes, per-bin totals and
     // bases, the bin-partitioned staging (reference + in-bin bucket), the partial-level offsets and
     // their per-bin sums / prefixes, and the two hand-off tickets (zero between launches: the last
@@ -137,7 +140,7 @@ struct MsmPlan {
     bool compact = false;         // proof-sharded keys (only in-range digits, capacity tot_refs)
     double mu_max = 0;            // largest expected references per bucket over the active instances
     bool any_split = false;
-    // weighting tree: per instance, node offset and node count after the chunked leaf; levels above it
+    // weighting tree: per instance, slot offset and chunk count (slots of its F and of its S array); levels above the leaf
     std::vector<uint32_t> node_off, cnt;
     int levels = 0;     // tree levels above the leaf (max over instances)
     int top_from = 1;   // first level done by k_tree_top (all levels >= it); levels below run one launch each

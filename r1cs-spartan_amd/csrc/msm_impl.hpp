@@ -352,18 +352,28 @@ __global__ __launch_bounds__(kHotThreads, 1) void k_accum_hot(const uint32_t* __
 }
 
 // ------------------------------------------------------------------ bucket weighting: chunks + tree
-// Result = sum_j (j+1) S_j over the B = 2^(c-1) bucket sums of an instance. Node = (F, S, D) over a
-// run of consecutive buckets, with F = sum_m (m+1) X_m (local index m), S = sum X_m, D = size * S.
-// Leaf level, chunked (k_tree_chunk): one thread sums m = 2^lgm consecutive buckets by a running
-// sum (from the top bucket down: run += X_j, F += run), giving the chunk's node (F, S, D = m S) in
-// 2m additions + lgm doublings (a pairwise tree spends ~5 group operations per bucket on the
-// levels this replaces). Above it, a binary tree over the chunks:
-//   parent(l, r) = (F_l + D_r + F_r,  S_l + S_r,  2 (D_l + D_r))      (size(l) = size(r))
-// one level per launch, one thread per (node, component), component-major so every wave runs one
-// component (no divergence between the F / S / D formulas): 2 group operations of dependent
-// depth per level (single-lane latency of a G2 addition is ~45 us on CDNA4).
-// A missing right child (instances with fewer chunks) is the point at infinity: F and S pass
-// through unchanged, so all instances of a batch run the same number of levels.
+// Result = sum_u (u+1) X_u over the B = 2^lb bucket sums of an instance, in chunks of m = 2^lgm:
+// with F_k = sum_{j<m} (j+1) X_{km+j} and S_k = sum_j X_{km+j} of chunk k,
+//   sum_u (u+1) X_u = F0 + m sum_l 2^l U_l,   F0 = sum_k F_k,   U_l = sum of S_k over the k with bit l set.
+// The multiplier of a right subtree depends on its level alone, so it is applied once per level at
+// the root instead of once per node: below the root there are only additions, and no doubling.
+// Leaf level, chunked (k_tree_chunk): one thread sums m consecutive buckets by a running sum (from
+// the top bucket down: run += X_j, F += run), giving (F_k, S_k) in 2m additions (a pairwise tree
+// spends ~5 group operations per bucket on the levels this replaces).
+// Above it every level is a + b in place, one level per launch (k_tree_level), one thread per sum,
+// every thread the same code. Level R (R = 1, 2, ..; h = 2^(R-1)) runs, on the S array,
+//   S[x] += S[x + h]   for every x = j 2^R + r,  r = 0 or r = 2^l with l < R - 1
+// and F[x] += F[x + h] for x = j 2^R. Residue 0 is the plain S-tree (S[j 2^R] = sum of the subtree
+// of 2^R chunks at j 2^R). Its right children, the slots x = 2^(R-1) (mod 2^R), are exactly the
+// subtrees whose chunks have bit R - 1 set: the S-tree only reads them, so they stay as they are and
+// ARE the start of U_(R-1), which the later levels halve where it lies (residue r = 2^(R-1)). A
+// level reads slots with bit R - 1 set and writes slots with it clear, so no slot is both read and
+// written in a launch and nothing is copied. After level R the live slots are S: x = j 2^R,
+// U_l (l < R): x = j 2^R + 2^l; after all L = lb - lgm levels S[0] is the sum of all buckets and
+// S[2^l] = U_l. R + 1 sums per 2^R chunks at level R: 3 additions per chunk over all levels, and
+// one addition of dependent depth per level (single-lane latency of a G2 addition is ~45 us on CDNA4).
+// A sum without a partner (x + h past the instance's chunks: instances with fewer chunks than the
+// batch's widest) stays as it is, so all instances of a batch run the same number of levels.
 // lb = log2 of the instance's (local) buckets >= 1; chunks of 2^lgm buckets, lgm <= lb - 1
 DEV uint32_t tree_chunk_log(uint32_t lb) { return lb - 1 < kTreeChunkLog ? lb - 1 : kTreeChunkLog; }
 
@@ -376,7 +386,7 @@ template <class F>
 __global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_tree_chunk(
     const MsmInst* __restrict__ insts, const uint64_t* __restrict__ wp, int ninst, const uint32_t* __restrict__ node_off,
     const uint32_t* __restrict__ off, const Xyzz<F>* __restrict__ P,
-    Xyzz<F>* __restrict__ Fo, Xyzz<F>* __restrict__ So, Xyzz<F>* __restrict__ Do, uint32_t hot_on, uint32_t* __restrict__ st) {
+    Xyzz<F>* __restrict__ Fo, Xyzz<F>* __restrict__ So, uint32_t hot_on, uint32_t* __restrict__ st) {
     using A = Acc<F>;
     const uint64_t t = tree_elem<F>();
     if (t >= wp[ninst]) return;
@@ -434,146 +444,152 @@ __global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_tree_chunk(
         }
     }
     A::st(So + o, run);
-#pragma unroll 1
-    for (uint32_t d = 0; d < lgm; ++d) tree_dbl<F>(run);
-    A::st(Do + o, run);
 }
 
+// Level R, in place (see above): element (sum c, node k of the level's wp) is slot x = k 2^R + r of
+// the F array (c = 0, r = 0) or the S array (c = 1: r = 0; c >= 2: r = 2^(c - 2)); c-major, so a wave
+// runs one sum. cnt: the instance's chunks (slots per array).
 template <class F>
-__global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_tree_level(
-    const uint64_t* __restrict__ wp, int ninst, const uint32_t* __restrict__ node_off, const uint32_t* __restrict__ cnt_in,
-    const Xyzz<F>* __restrict__ Fi, const Xyzz<F>* __restrict__ Si, const Xyzz<F>* __restrict__ Di,
-    Xyzz<F>* __restrict__ Fo, Xyzz<F>* __restrict__ So, Xyzz<F>* __restrict__ Do) {
+__global__ __launch_bounds__(kHeavy, Acc<F>::kWaves) void k_tree_level(const uint64_t* __restrict__ wp, int ninst,
+                                                                       const uint32_t* __restrict__ node_off,
+                                                                       const uint32_t* __restrict__ cnt, uint32_t R,
+                                                                       Xyzz<F>* Fa, Xyzz<F>* Sa) {
     using A = Acc<F>;
     const uint64_t t = tree_elem<F>();
     const uint64_t N = wp[ninst];
-    if (t >= 3 * N) return;
+    if (t >= (R + 1) * N) return;
     const uint32_t comp = (uint32_t)(t / N);
     const uint64_t tn = t - comp * N;
     const int i = find_slot(wp, ninst, tn);
     const uint32_t k = (uint32_t)(tn - wp[i]);
-    const uint32_t base = node_off[i], n = cnt_in[i];
-    const bool has_r = 2 * k + 1 < n;
+    const uint32_t h = 1u << (R - 1);
+    const uint32_t x = (k << R) + (comp < 2 ? 0u : 1u << (comp - 2));
+    if (x + h >= cnt[i]) return;  // no partner: the sum stays as it is
+    Xyzz<F>* p = (comp == 0 ? Fa : Sa) + node_off[i] + x;
     X29<typename A::T> a, b;
-    if (comp == 0) {  // F_l + D_r + F_r
-        A::ld(a, Fi + base + 2 * k);
-        if (has_r) {
-            A::ld(b, Di + base + 2 * k + 1);
-            tree_add<F>(a, b);
-            A::ld(b, Fi + base + 2 * k + 1);
-            tree_add<F>(a, b);
-        }
-        A::st(Fo + base + k, a);
-    } else if (comp == 1) {
-        A::ld(a, Si + base + 2 * k);
-        if (has_r) {
-            A::ld(b, Si + base + 2 * k + 1);
-            tree_add<F>(a, b);
-        }
-        A::st(So + base + k, a);
-    } else {
-        A::ld(a, Di + base + 2 * k);
-        if (has_r) {  // a lone root passes through (its D is never read again)
-            A::ld(b, Di + base + 2 * k + 1);
-            tree_add<F>(a, b);
-            tree_dbl<F>(a);
-        }
-        A::st(Do + base + k, a);
-    }
+    A::ld(a, p);
+    A::ld(b, p + h);
+    tree_add<F>(a, b);
+    A::st(p, a);
 }
 
-// The top levels of every instance's weighting tree in ONE launch: one workgroup per instance, its
-// nodes in LDS (the levels whose input has <= kTopNodes = 32 nodes; each is 2 dependent additions, so
-// launching them one by one cost a launch gap per level). Then, for an instance split over the ranks
-// (this rank holds buckets u = sel + G k, G = 2^lg, as local buckets k, and the tree computed
-// F = sum_k (k + 1) X_k, S = sum_k X_k), the rank's share sum_k (sel + G k + 1) X_k = G F - (G - 1 - sel) S;
-// finally the R = 2^384 Montgomery output for the host.
+// The top levels of every instance's weighting tree and its root in ONE launch: one workgroup per
+// instance, its live sums in LDS (launching these levels one by one cost a launch gap per level).
+// Handed over after level R0 with n = max(1, chunks >> R0) nodes per array: S (n slots here), and F
+// and the nu = min(R0, L) sums U_l already begun (slots S[k 2^R0 + 2^l]), which are plain halvings:
+// their first one here reads global memory, so each takes n / 2 slots. The plan (msm_plan) takes the
+// first R0 at which n + (R0 + 1) n / 2 <= kTopElems for the batch's widest instance, n <= kTopNodes.
+// The levels go on in place as in k_tree_level: the local S array is residue 0 of the global one, so
+// U_l for l >= R0 grows in it at slot 2^(l - R0).
+// Root: the value is a sum of at most L + 2 <= 23 terms, each a power of two times one of the sums,
+//   2^lg F0  +  sum_{l < L} 2^(lg + lgm + l) U_l  -  (G - 1 - sel) S
+// (lg = 0 and no last term for a whole instance; for one split over the ranks, G = 2^lg, this rank
+// holds buckets u = sel + G k as local buckets k and its share is sum_k (sel + G k + 1) X_k =
+// G V - (G - 1 - sel) S with V the local value). One lane group per term runs its doublings, all at
+// once (at most c - 2 deep), then the terms are added pairwise (5 additions deep); finally the
+// R = 2^384 Montgomery output for the host.
 static constexpr int kTopThreads = 128;
 template <class F>
 __global__ __launch_bounds__(kTopThreads, 1) void k_tree_top(const MsmInst* __restrict__ insts, int nact,
                                                              const uint32_t* __restrict__ node_off,
-                                                             const uint32_t* __restrict__ cin_top, int lv0, int levels,
+                                                             const uint32_t* __restrict__ cnt, uint32_t R0,
                                                              const Xyzz<F>* __restrict__ Fi, const Xyzz<F>* __restrict__ Si,
-                                                             const Xyzz<F>* __restrict__ Di, Xyzz<F>* __restrict__ out) {
+                                                             Xyzz<F>* __restrict__ out) {
     using A = Acc<F>;
     using T = typename A::T;
     using O = Ops29<T>;
     constexpr int kL = TreeLanes<F>::v;
-    __shared__ Xyzz<F> buf[2][3][kTopNodes];
+    constexpr uint32_t ngrp = kTopThreads / kL;
+    static_assert(ngrp >= 25, "one lane group per term of the root (c <= 24: at most 23)");
+    __shared__ Xyzz<F> buf[kTopElems];
     const int i = blockIdx.x;
     const MsmInst I = insts[i];
     const uint32_t base = node_off[i];
-    const int grp = threadIdx.x / kL, ngrp = kTopThreads / kL;
-    // the instance's node count after the leaf: its input at lv0 is max(1, cnt >> (lv0 - 1))
-    uint32_t nin = cin_top[i];
-    for (uint32_t t = threadIdx.x; t < 3 * nin; t += blockDim.x) {
-        const uint32_t comp = t / nin, k = t % nin;
-        const Xyzz<F>* src = comp == 0 ? Fi : (comp == 1 ? Si : Di);
-        buf[0][comp][k] = src[base + k];
-    }
+    const uint32_t grp = threadIdx.x / kL;
+    const uint32_t lgm = tree_chunk_log(I.lb), L = I.lb - lgm;
+    const uint32_t n = max(1u, cnt[i] >> R0), n2 = max(1u, n >> 1);
+    const uint32_t nu = min(R0, L), ns = 1 + nu;  // plain arrays: F, then U_l for l < nu
+    // buf: S [0, n), then plain array j at n + j n2 (its first halving reads global memory)
+    const auto plain_src = [&](uint32_t j) { return (j == 0 ? Fi : Si + (1u << (j - 1))) + base; };
+    for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) buf[t] = Si[base + (t << R0)];
+    if (n == 1)
+        for (uint32_t j = threadIdx.x; j < ns; j += blockDim.x) buf[1 + j] = *plain_src(j);
     __syncthreads();
-    int cur = 0;
-    for (int lv = lv0; lv <= levels; ++lv) {
-        const uint32_t nout = nin > 1 ? nin / 2 : 1;
-        for (uint32_t task = grp; task < 3 * nout; task += ngrp) {
+    for (uint32_t r = 1; (1u << r) <= n; ++r) {
+        const uint32_t h = 1u << (r - 1), nout = n >> r, per = r + ns;  // sums per output node
+        for (uint32_t task = grp; task < per * nout; task += ngrp) {
             const uint32_t comp = task / nout, k = task % nout;
-            const bool has_r = 2 * k + 1 < nin;
+            uint32_t dst;
             X29<T> a, b;
-            A::ld(a, &buf[cur][comp][2 * k]);
-            if (comp == 0) {  // F_l + D_r + F_r
-                if (has_r) {
-                    A::ld(b, &buf[cur][2][2 * k + 1]);
-                    tree_add<F>(a, b);
-                    A::ld(b, &buf[cur][0][2 * k + 1]);
-                    tree_add<F>(a, b);
+            if (comp < r) {  // S: residue 0 or 2^(comp - 1)
+                dst = (k << r) + (comp == 0 ? 0u : 1u << (comp - 1));
+                A::ld(a, &buf[dst]);
+                A::ld(b, &buf[dst + h]);
+            } else {
+                const uint32_t j = comp - r;
+                if (r == 1) {
+                    const Xyzz<F>* src = plain_src(j);
+                    dst = n + j * n2 + k;
+                    A::ld(a, src + ((2 * k) << R0));
+                    A::ld(b, src + ((2 * k + 1) << R0));
+                } else {
+                    dst = n + j * n2 + (k << (r - 1));
+                    A::ld(a, &buf[dst]);
+                    A::ld(b, &buf[dst + (h >> 1)]);
                 }
-            } else if (has_r) {  // S_l + S_r; 2 (D_l + D_r)
-                A::ld(b, &buf[cur][comp][2 * k + 1]);
-                tree_add<F>(a, b);
-                if (comp == 2) tree_dbl<F>(a);
             }
-            A::st(&buf[cur ^ 1][comp][k], a);
+            tree_add<F>(a, b);
+            A::st(&buf[dst], a);
         }
         __syncthreads();
-        cur ^= 1;
-        nin = nout;
     }
-    if (I.lg) {  // the rank's share of a split instance: G F - (G - 1 - sel) S, the two products side by side
-        const uint32_t k = (1u << I.lg) - 1 - I.sel;
-        if (grp == 0) {  // G F: lg doublings
-            X29<T> f;
-            A::ld(f, &buf[cur][0][0]);
+    // the root's terms, one lane group each: 0: F0, 1 + l: U_l, L + 1: -(G - 1 - sel) S
+    const uint32_t ks = I.lg ? (1u << I.lg) - 1 - I.sel : 0;
+    const uint32_t nterm = L + 1 + (ks ? 1 : 0);
+    X29<T> v;
+    if (grp < nterm) {
+        if (grp == L + 1) {  // -(ks S): double-and-add below the top bit
+            X29<T> sv;
+            A::ld(sv, &buf[0]);
+            v = sv;
 #pragma unroll 1
-            for (uint32_t d = 0; d < I.lg; ++d) tree_dbl<F>(f);
-            A::st(&buf[cur][0][0], f);
-        } else if (grp == 1 && k) {  // -(k S): double-and-add below the top bit, into the free slot
-            X29<T> sv, acc;
-            A::ld(sv, &buf[cur][1][0]);
-            acc = sv;
-#pragma unroll 1
-            for (int b = 30 - __clz(k); b >= 0; --b) {
-                tree_dbl<F>(acc);
-                if ((k >> b) & 1u) tree_add<F>(acc, sv);
+            for (int b = 30 - __clz(ks); b >= 0; --b) {
+                tree_dbl<F>(v);
+                if ((ks >> b) & 1u) tree_add<F>(v, sv);
             }
             T z;
             O::zero(z);
-            O::template sub<2>(acc.y, z, acc.y);  // y < 2p -> 2p - y < 2p
-            A::st(&buf[cur][1][1], acc);
-        }
-        __syncthreads();
-        if (grp == 0 && k) {
-            X29<T> f, acc;
-            A::ld(f, &buf[cur][0][0]);
-            A::ld(acc, &buf[cur][1][1]);
-            tree_add<F>(f, acc);
-            A::st(&buf[cur][0][0], f);
+            O::template sub<2>(v.y, z, v.y);  // y < 2p -> 2p - y < 2p
+        } else {
+            uint32_t src = n, nd = I.lg;
+            if (grp) {
+                const uint32_t l = grp - 1;
+                src = l < nu ? n + (1 + l) * n2 : 1u << (l - R0);
+                nd += lgm + l;
+            }
+            A::ld(v, &buf[src]);
+#pragma unroll 1
+            for (uint32_t d = 0; d < nd; ++d) tree_dbl<F>(v);
         }
     }
+    __syncthreads();  // every term is read before the first is stored over the sums
+    if (grp < nterm) A::st(&buf[grp], v);
     __syncthreads();
+    for (uint32_t s = 1; s < nterm; s <<= 1) {
+        const uint32_t x = 2 * s * grp;
+        if (x + s < nterm) {
+            X29<T> a, b;
+            A::ld(a, &buf[x]);
+            A::ld(b, &buf[x + s]);
+            tree_add<F>(a, b);
+            A::st(&buf[x], a);
+        }
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {  // back to the R = 2^384 Montgomery domain, canonical, for the host
         using T1 = typename R29<F>::T;
         X29<T1> a, b;
-        ld29<F>(a, &buf[cur][0][0]);
+        ld29<F>(a, &buf[0]);
         f29_map(b.x, a.x, Q29::TO_R1);
         f29_map(b.y, a.y, Q29::TO_R1);
         f29_map(b.zz, a.zz, Q29::TO_R1);
@@ -664,26 +680,23 @@ static void msm_run_t(MsmWorkspace* ws, const MsmInst* ih, int ninst, const type
     // bucket weighting tree over each instance's 2^lb local buckets: leaf, middle levels, top
     uint32_t tot_nodes = 0;
     for (int i = 0; i < nact; ++i) tot_nodes += pl.cnt[i];
-    auto* TA = (Xyzz<F>*)ws->tree_a.ensure(3 * psz * std::max<uint32_t>(tot_nodes, 1));
-    auto* TB = (Xyzz<F>*)ws->tree_b.ensure(3 * psz * std::max<uint32_t>(tot_nodes, 1));
-    Xyzz<F>* A3[3] = {TA, TA + tot_nodes, TA + 2 * (size_t)tot_nodes};
-    Xyzz<F>* B3[3] = {TB, TB + tot_nodes, TB + 2 * (size_t)tot_nodes};
+    // the F and the S array, one slot per chunk each; the levels work in place
+    auto* TF = (Xyzz<F>*)ws->tree_a.ensure(2 * psz * std::max<uint32_t>(tot_nodes, 1));
+    auto* TS = TF + tot_nodes;
+    const uint32_t* d_cnt = pl.d_cin + nact;  // level 1's input: the instance's chunks
     kp_begin(g2 ? KP_RED_G2 : KP_RED_G1, s);
     {
         uint64_t work = pl.wp[nact];
         hipLaunchKernelGGL(k_tree_chunk<F>, dim3(tree_blocks<F>(work)), dim3(kHeavy), 0, s, pl.d_insts, pl.d_wp, nact,
-                           pl.d_noff, cur_off, cur, A3[0], A3[1], A3[2], ws->hot_on ? 1u : 0u, stw);
+                           pl.d_noff, cur_off, cur, TF, TS, ws->hot_on ? 1u : 0u, stw);
     }
     for (int lv = 1; lv < pl.top_from; ++lv) {
-        uint64_t work = 3 * pl.wp[(size_t)lv * (nact + 1) + nact];
+        uint64_t work = (uint64_t)(lv + 1) * pl.wp[(size_t)lv * (nact + 1) + nact];
         hipLaunchKernelGGL(k_tree_level<F>, dim3(tree_blocks<F>(work)), dim3(kHeavy), 0, s,
-                           pl.d_wp + (size_t)lv * (nact + 1), nact, pl.d_noff, pl.d_cin + (size_t)lv * nact, A3[0], A3[1],
-                           A3[2], B3[0], B3[1], B3[2]);
-        std::swap(A3, B3);
+                           pl.d_wp + (size_t)lv * (nact + 1), nact, pl.d_noff, d_cnt, (uint32_t)lv, TF, TS);
     }
-    hipLaunchKernelGGL(k_tree_top<F>, dim3(nact), dim3(kTopThreads), 0, s, pl.d_insts, nact, pl.d_noff,
-                       pl.d_cin + (size_t)pl.top_from * nact, pl.top_from, pl.levels, A3[0], A3[1], A3[2],
-                       (Xyzz<F>*)out_dev);
+    hipLaunchKernelGGL(k_tree_top<F>, dim3(nact), dim3(kTopThreads), 0, s, pl.d_insts, nact, pl.d_noff, d_cnt,
+                       (uint32_t)(pl.top_from - 1), TF, TS, (Xyzz<F>*)out_dev);
     kp_end((double)nb * psz, s);
     HIPCHK(hipGetLastError());
 }
