@@ -99,6 +99,33 @@ struct Sc1Group {
 struct Sc2Group {
     Sc2Job j[kGroupMax];
 };
+// the other steps' jobs: one per proof, as the sumcheck rounds'
+struct SpmvJob {
+    const Fr* z;
+    Fr* o[3];  // Az, Bz, Cz
+};
+struct EqTableJob {
+    const Fr* r;   // nvar device Fr
+    Fr* out;       // count Fr
+    Fr *lo, *hi;   // scratch tables, 2^13 Fr each
+};
+struct ColStreamJob {
+    const Fr* r_x;    // L device Fr
+    const Fr* scale;  // 3 device Fr
+    Fr* out;
+    Fr* eq_scratch;  // kEqScratch Fr
+    Fr* partial;     // the long columns' chunk sums (one Fr per chunk; unused without long columns)
+};
+struct OpenEvalJob {
+    const Fr* z;        // 2^L Fr
+    Fr *bufA, *bufB;    // 2^L / 2 and 2^L / 4 Fr: step s of the chain writes buffer s & 1
+    const Fr* points;   // L host Fr
+    Fr* last;           // receives z(points); null: the value stays where the chain leaves it (open_eval_result)
+};
+struct CopyJob {  // up to 3 runs of `per` Fr -> dst, back to back
+    const Fr* src[3];
+    Fr* dst;
+};
 
 // ---- live kernel statistics (HIP events around selected launches; off unless enabled)
 struct KProf {
@@ -229,7 +256,6 @@ void launch_index_long_fill(const LongRow* lrows, int nlrows, const LongChunk* c
 // ---- mle_kernels.hip
 void launch_to_mont(Fr* d, size_t n, int* err, hipStream_t s);
 void launch_from_mont(Fr* out, const Fr* in, size_t n, hipStream_t s);
-void launch_spmv_sliced(const SpmvSlicedView& v, const Fr* z, Fr* o0, Fr* o1, Fr* o2, uint64_t entries, hipStream_t s);
 void launch_sparse3(int mode, const SparseView3& mv, const Fr* vec, Fr* o0, Fr* o1, Fr* o2, const Fr* scale,
                     uint64_t count, const LongChunk* chunks, int nchunks, const LongRow* lrows, int nlrows,
                     Fr* partial, hipStream_t s);
@@ -244,47 +270,57 @@ struct EqFactors {
 // the split used for L variables, tables carved from `scratch` (kEqScratch Fr)
 static constexpr uint64_t kEqScratch = 4 * 8192;
 EqFactors eq_factors_for(int L, Fr* scratch);
-// out[y] = sum_m scale[m] sum_x eq(r_x, x) M[x][y] over the column stream (r_x: L device Fr, scale: 3),
-// then the long columns' chunks (over `lv`'s per-matrix entry arrays) added in
-void launch_col_stream(const ColStreamView& cv, const Fr* r_x, int L, const Fr* scale, Fr* out, Fr* eq_scratch,
-                       const SparseView3& lv, const LongChunk* chunks, int nchunks, const LongRow* lrows, int nlrows,
-                       Fr* partial, hipStream_t s);
-void launch_eq_table(const Fr* r_dev, int k, uint64_t base, uint64_t count, Fr* out, Fr* scratch_lo,
-                     Fr* scratch_hi, hipStream_t s);
+// Every launcher below takes the jobs of k proofs (1 <= k <= kGroupMax), as launch_r1cs_check. k == 1
+// is the per-proof launch (prove()); k > 1 is ONE launch for a lockstep group, proof j's blocks at
+// blockIdx.y = j, running the per-proof kernels' bodies, so each proof's outputs are bit-identical
+// to its own launch's. Shapes without a group kernel launch per proof inside the launcher.
+//
+// SpMV over the column-sorted entry list into jobs[j].o = (Az, Bz, Cz) (k > 1: the entries are
+// streamed once for the group)
+void launch_spmv_sliced(int k, const SpmvJob* jobs, const SpmvSlicedView& v, uint64_t entries, hipStream_t s);
+// out[i] = eq(r, base + i), i < count, over nvar (<= 26) variables
+void launch_eq_table(int k, const EqTableJob* jobs, int nvar, uint64_t base, uint64_t count, hipStream_t s);
+// out[y] = sum_m scale[m] sum_x eq(r_x, x) M[x][y] over the column stream, then the long columns' chunks
+// (over `lv`'s per-matrix entry arrays) added in; an index with long columns launches per proof
+void launch_col_stream(int k, const ColStreamJob* jobs, const ColStreamView& cv, int L, const SparseView3& lv,
+                       const LongChunk* chunks, int nchunks, const LongRow* lrows, int nlrows, hipStream_t s);
 int sc_grid(uint64_t half);
 // A round: fold with the previous challenge r (by value; unused in round 1), evaluate the round
 // polynomial at 0, 1, 2 (at 1 only if need1: otherwise result3[1] = 0 and the caller derives it from
 // the previous claim), and reduce over the blocks into result3 (3 Fr; device or host-mapped pinned
 // memory) - in the last block for small grids, by a second one-block launch otherwise.
 // partial: kRoundPartials Fr of scratch (3 per block; the quad / lane-pair and wave forms launch more
-// blocks than sc_grid(half)); ticket: a device counter that is 0 (left 0).
-void launch_sc1_round(bool fold, const Tables3& in, const Tables3& out, const Fr* Ein, Fr* Eout, const Fr& r,
-                      uint64_t half, Fr* partial, uint32_t* ticket, Fr* result3, bool need1, hipStream_t s);
-void launch_sc2_round(bool fold, const Fr* Min, const Fr* Zin, Fr* Mout, Fr* Zout, const Fr& r, uint64_t half,
-                      Fr* partial, uint32_t* ticket, Fr* result3, bool need1, hipStream_t s);
-// launch_sc1_round / launch_sc2_round for the k (<= kGroupMax) proofs of a lockstep group, in ONE launch
-// (and one reduction launch for large grids): the same kernels' arithmetic, so each proof's result3
-// equals its own launch's. need1 applies to every proof of the group.
-void launch_sc1_round_group(int k, bool fold, const Sc1Job* jobs, uint64_t half, bool need1, hipStream_t s);
-void launch_sc2_round_group(int k, bool fold, const Sc2Job* jobs, uint64_t half, bool need1, hipStream_t s);
-// the other steps of a lockstep group, one launch per step for the k proofs (each proof's arguments as
-// its own launch would take them; outputs bit-identical to the per-proof launchers):
-// SpMV over the column-sorted entry list into out[j] = (Az, Bz, Cz);
-void launch_spmv_sliced_group(int k, const SpmvSlicedView& v, const Fr* const* z, const Tables3* out, uint64_t entries,
-                              hipStream_t s);
-// launch_eq_table per proof (nvar variables at r_dev[j], scratch tables lo[j], hi[j]);
-void launch_eq_table_group(int k, const Fr* const* r_dev, int nvar, uint64_t base, uint64_t count, Fr* const* out,
-                           Fr* const* lo, Fr* const* hi, hipStream_t s);
-// launch_col_stream per proof, for an index without long columns (the caller checks);
-void launch_col_stream_group(int k, const ColStreamView& cv, const Fr* const* r_x, int L, const Fr* const* scale,
-                             Fr* const* out, Fr* const* eq_scratch, hipStream_t s);
-// z_j(points_j) by the stubbed opening's fold chain (no quotients), the value written to last[j]
-// (host-mapped pinned memory allowed); bufA / bufB: n/2 and n/4 Fr per proof; points: k x L Fr
-void launch_open_eval_group(int k, const Fr* const* z, Fr* const* bufA, Fr* const* bufB, const Fr* points, int L,
-                            uint64_t n, Fr* const* last, hipStream_t s);
-// per proof j: nruns (<= 3) runs of `per` Fr (nruns x per <= 4096) from src[j].t[i] to dst[j] back to back,
-// one launch
-void launch_copy_runs_group(int k, const Tables3* src, int nruns, int per, Fr* const* dst, hipStream_t s);
+// blocks than sc_grid(half)); ticket: a device counter that is 0 (left 0). fold and need1 apply to
+// every proof. Small rounds that need G(1) / P(1), and a round 1 below 2^14 pairs, have no group kernel.
+void launch_sc1_round(int k, const Sc1Job* jobs, bool fold, bool need1, uint64_t half, hipStream_t s);
+void launch_sc2_round(int k, const Sc2Job* jobs, bool fold, bool need1, uint64_t half, hipStream_t s);
+// what a round launches: the kernel form, its grid per proof, whether the last block reduces (else a
+// second launch does), and whether the k proofs are launched one by one. The one place that decides.
+enum { kRoundLane = 0, kRoundSplit = 1, kRoundWave = 2 };  // split: a quad (sumcheck 1) / lane pair (2) per pair
+struct RoundPlan {
+    int form, grid;
+    bool fused, per_proof;
+};
+RoundPlan sc_round_plan(int which, int k, bool fold, bool need1, uint64_t half);
+// z(points) of an L-variable table by the opening's fold chain without quotients (the stubbed opening):
+// the steps, each writing the buffer its index selects (bufA, bufB, bufA, ...). copy: the chain ends on a
+// fold, whose one-entry output is then copied to `last` (where the job names one).
+enum { kOpenTail = 0, kOpenFold = 1, kOpenLevel = 2 };
+struct OpenStep {
+    int kind, first, levels;  // levels [first, first + levels) of the chain
+    uint64_t size;            // tail, level: pairs going in; fold: entries coming out
+    bool wave;                // fold: the wave-transposed kernel
+};
+struct OpenEvalPlan {
+    std::vector<OpenStep> steps;
+    bool copy;
+};
+OpenEvalPlan open_eval_plan(int L);
+void launch_open_eval(int k, const OpenEvalJob* jobs, int L, hipStream_t s);
+// where launch_open_eval leaves the job's value: `last`, or the chain's last output if the job names none
+const Fr* open_eval_result(const OpenEvalJob& job, int L);
+// per proof j: nruns (<= 3) runs of `per` Fr (nruns x per <= 4096) from src[i] to dst back to back, one launch
+void launch_copy_runs(int k, const CopyJob* jobs, int nruns, int per, hipStream_t s);
 void launch_open_level(const Fr* rin, Fr* rout, Fr* q, const Fr& point, uint64_t half, hipStream_t s);
 // Witness check (k_r1cs_check): over the rank-local tables Az, Bz, Cz (nl rows each, row0 =
 // the global index of local row 0) the rows with Az[i] Bz[i] != Cz[i] are counted and the lowest one is

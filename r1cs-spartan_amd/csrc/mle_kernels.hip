@@ -1191,10 +1191,7 @@ template <class J, int N = kGroupMax>
 struct GroupOf {
     J j[N];
 };
-struct SpmvJob {
-    const Fr* z;
-    Fr* o[3];
-};
+// (SpmvJob and CopyJob are the callers' own: kernels.hpp)
 struct EqfJob {
     const Fr* r;
     EqFactors ef;
@@ -1224,10 +1221,6 @@ struct TailJob {
     const Fr* rin;
     Fr* last;
     TailPoints pts;
-};
-struct CopyJob {  // up to 3 runs of `per` Fr -> dst, back to back
-    const Fr* src[3];
-    Fr* dst;
 };
 // The group's SpMVs share one index: each entry (value, column, row | matrix: 40 B) is streamed ONCE
 // and applied to the k proofs' z in turn (gather, product, store per proof), instead of once per
@@ -1441,11 +1434,40 @@ void launch_from_mont(Fr* out, const Fr* in, size_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_from_mont, dim3(grid_for(n, 4096)), dim3(kThreads), 0, s, out, in, n);
 }
 
-void launch_spmv_sliced(const SpmvSlicedView& v, const Fr* z, Fr* o0, Fr* o1, Fr* o2, uint64_t entries, hipStream_t s) {
-    // 8 x Q workgroups (a multiple of the 8 XCDs), at most 2 chunks' worth of workgroups per range
+static void check_group(int k) {
+    if (k < 1 || k > kGroupMax) throw std::invalid_argument("lockstep group size out of range");
+}
+// the jobs of k proofs as a group launch's by-value argument
+template <class Group, class Job>
+static Group group_of(int k, const Job* jobs) {
+    check_group(k);
+    Group g{};
+    for (int i = 0; i < k; ++i) g.j[i] = jobs[i];
+    return g;
+}
+// a run-time bool as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static void with_bool(bool b, F f) {
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+#define SPX_BV(x) decltype(x)::value
+
+void launch_spmv_sliced(int k, const SpmvJob* jobs, const SpmvSlicedView& v, uint64_t entries, hipStream_t s) {
+    check_group(k);
+    // 8 x Q workgroups (a multiple of the 8 XCDs). One proof: at most 2 chunks' worth of workgroups per
+    // range. A group: as many workgroups as chunks, each doing k proofs' products per entry.
     const uint64_t per_xcd = (entries / 8 + kThreads * kSpmvPer - 1) / (kThreads * kSpmvPer);
-    const unsigned Q = (unsigned)std::min<uint64_t>(256, std::max<uint64_t>(1, (per_xcd + 1) / 2));
-    hipLaunchKernelGGL(k_spmv_sliced, dim3(8 * Q), dim3(kThreads), 0, s, v, z, o0, o1, o2, entries);
+    const unsigned Q = (unsigned)std::min<uint64_t>(256, std::max<uint64_t>(1, k == 1 ? (per_xcd + 1) / 2 : per_xcd));
+    if (k == 1) {
+        hipLaunchKernelGGL(k_spmv_sliced, dim3(8 * Q), dim3(kThreads), 0, s, v, jobs[0].z, jobs[0].o[0], jobs[0].o[1],
+                           jobs[0].o[2], entries);
+    } else {
+        const GroupOf<SpmvJob> g = group_of<GroupOf<SpmvJob>>(k, jobs);
+        hipLaunchKernelGGL(k_spmv_sliced_group, dim3(8 * Q), dim3(kThreads), 0, s, v, g, k, entries);
+    }
 }
 void launch_sparse3(int mode, const SparseView3& mv, const Fr* vec, Fr* o0, Fr* o1, Fr* o2, const Fr* scale,
                     uint64_t count, const LongChunk* chunks, int nchunks, const LongRow* lrows, int nlrows,
@@ -1480,38 +1502,64 @@ EqFactors eq_factors_for(int L, Fr* scratch) {
     return ef;
 }
 
-void launch_col_stream(const ColStreamView& cv, const Fr* r_x, int L, const Fr* scale, Fr* out, Fr* eq_scratch,
-                       const SparseView3& lv, const LongChunk* chunks, int nchunks, const LongRow* lrows, int nlrows,
-                       Fr* partial, hipStream_t s) {
-    const EqFactors ef = eq_factors_for(L, eq_scratch);
-    hipLaunchKernelGGL(k_eq_factors, dim3(ef.nf), dim3(kEqThreads), 0, s, r_x, ef, scale);
-    if (cv.nslices) {
-        const uint32_t nwin = (cv.nslices + kColWindow - 1) / kColWindow;
-        hipLaunchKernelGGL(k_col_stream, dim3(nwin), dim3(kThreads), 0, s, cv, ef, out);
+void launch_col_stream(int k, const ColStreamJob* jobs, const ColStreamView& cv, int L, const SparseView3& lv,
+                       const LongChunk* chunks, int nchunks, const LongRow* lrows, int nlrows, hipStream_t s) {
+    GroupOf<EqfJob> gf{};
+    GroupOf<ColJob> gc{};
+    check_group(k);
+    for (int i = 0; i < k; ++i) {
+        const EqFactors ef = eq_factors_for(L, jobs[i].eq_scratch);
+        gf.j[i] = EqfJob{jobs[i].r_x, ef, jobs[i].scale};
+        gc.j[i] = ColJob{ef, jobs[i].out};
     }
-    if (nchunks > 0) {
-        hipLaunchKernelGGL(k_col_chunks, dim3(nchunks), dim3(kThreads), 0, s, lv, ef, chunks, partial);
-        hipLaunchKernelGGL(k_sparse_long_finish<0>, dim3(1), dim3(64), 0, s, lrows, nlrows, partial, out, out, out,
-                           nullptr);
+    const int nf = gf.j[0].ef.nf;
+    const uint32_t nwin = (cv.nslices + kColWindow - 1) / kColWindow;
+    if (k > 1 && nchunks == 0) {
+        hipLaunchKernelGGL(k_eq_factors_group, dim3(nf, k), dim3(kEqThreads), 0, s, gf);
+        if (cv.nslices) hipLaunchKernelGGL(k_col_stream_group, dim3(nwin, k), dim3(kThreads), 0, s, cv, gc);
+        return;
+    }
+    for (int i = 0; i < k; ++i) {  // one proof, or long columns (their chunks exist per proof only)
+        const EqFactors& ef = gc.j[i].ef;
+        hipLaunchKernelGGL(k_eq_factors, dim3(nf), dim3(kEqThreads), 0, s, jobs[i].r_x, ef, jobs[i].scale);
+        if (cv.nslices) hipLaunchKernelGGL(k_col_stream, dim3(nwin), dim3(kThreads), 0, s, cv, ef, jobs[i].out);
+        if (nchunks > 0) {
+            hipLaunchKernelGGL(k_col_chunks, dim3(nchunks), dim3(kThreads), 0, s, lv, ef, chunks, jobs[i].partial);
+            hipLaunchKernelGGL(k_sparse_long_finish<0>, dim3(1), dim3(64), 0, s, lrows, nlrows, jobs[i].partial,
+                               jobs[i].out, jobs[i].out, jobs[i].out, nullptr);
+        }
     }
 }
 
-void launch_eq_table(const Fr* r_dev, int k, uint64_t base, uint64_t count, Fr* out, Fr* scratch_lo,
-                     Fr* scratch_hi, hipStream_t s) {
-    // split k = klo + khi, each <= 13 (k <= 26): the scratch halves hold 2^13 entries
-    int klo = (k + 1) / 2, khi = k - klo;
-    if (k < 0 || klo > 13) throw std::invalid_argument("launch_eq_table: more than 26 variables");
-    EqFactors ef{};
-    ef.nf = 2;
-    ef.k[0] = klo;
-    ef.k[1] = khi;
-    ef.t[0] = scratch_lo;
-    ef.t[1] = scratch_hi;
-    hipLaunchKernelGGL(k_eq_factors, dim3(2), dim3(kEqThreads), 0, s, r_dev, ef, nullptr);
-    kp_begin(KP_EQ, s);
-    hipLaunchKernelGGL(k_eq_expand, dim3(grid_for(count, 8192)), dim3(kThreads), 0, s, scratch_lo, scratch_hi, klo, base,
-                       count, out);
-    kp_end(32.0 * (double)count, s);
+void launch_eq_table(int k, const EqTableJob* jobs, int nvar, uint64_t base, uint64_t count, hipStream_t s) {
+    // split nvar = klo + khi, each <= 13 (nvar <= 26): the scratch tables hold 2^13 entries
+    const int klo = (nvar + 1) / 2, khi = nvar - klo;
+    if (nvar < 0 || klo > 13) throw std::invalid_argument("launch_eq_table: more than 26 variables");
+    check_group(k);
+    GroupOf<EqfJob> gf{};
+    GroupOf<EqxJob> gx{};
+    for (int i = 0; i < k; ++i) {
+        EqFactors ef{};
+        ef.nf = 2;
+        ef.k[0] = klo;
+        ef.k[1] = khi;
+        ef.t[0] = jobs[i].lo;
+        ef.t[1] = jobs[i].hi;
+        gf.j[i] = EqfJob{jobs[i].r, ef, nullptr};
+        gx.j[i] = EqxJob{jobs[i].lo, jobs[i].hi, jobs[i].out};
+    }
+    const int g = grid_for(count, 8192);
+    if (k == 1) {
+        hipLaunchKernelGGL(k_eq_factors, dim3(2), dim3(kEqThreads), 0, s, jobs[0].r, gf.j[0].ef, nullptr);
+        kp_begin(KP_EQ, s);
+        hipLaunchKernelGGL(k_eq_expand, dim3(g), dim3(kThreads), 0, s, jobs[0].lo, jobs[0].hi, klo, base, count,
+                           jobs[0].out);
+    } else {
+        hipLaunchKernelGGL(k_eq_factors_group, dim3(2, k), dim3(kEqThreads), 0, s, gf);
+        kp_begin(KP_EQ, s);
+        hipLaunchKernelGGL(k_eq_expand_group, dim3(g, k), dim3(kThreads), 0, s, gx, klo, base, count);
+    }
+    kp_end(32.0 * (double)count * k, s);
 }
 
 int sc_grid(uint64_t half) { return grid_for(half, 1024); }
@@ -1523,299 +1571,237 @@ static constexpr int kFuseMaxBlocks = 64;
 // waves of 64 pairs; grids of <= kFuseMaxBlocks blocks reduce in their last block, as k_sc1_round)
 static constexpr uint64_t kWaveMinHalf = 1u << 14;
 static constexpr int kWaveMaxBlocks = (int)(kRoundPartials / 3);
-template <bool FOLD>
-static void sc1_launch(int g, const Tables3& in, const Tables3& out, const Fr* Ein, Fr* Eout, const Fr& r, uint64_t half,
-                       Fr* partial, uint32_t* ticket, Fr* result3, int need1, hipStream_t s) {
-    if (g <= kFuseMaxBlocks)
-        hipLaunchKernelGGL((k_sc1_round<FOLD, true>), dim3(g), dim3(kThreads), 0, s, in, out, Ein, Eout, r, half, partial,
-                           ticket, result3, need1);
-    else
-        hipLaunchKernelGGL((k_sc1_round<FOLD, false>), dim3(g), dim3(kThreads), 0, s, in, out, Ein, Eout, r, half, partial,
-                           ticket, result3, need1);
-}
-template <bool FOLD>
-static void sc2_launch(int g, const Fr* Min, const Fr* Zin, Fr* Mout, Fr* Zout, const Fr& r, uint64_t half, Fr* partial,
-                       uint32_t* ticket, Fr* result3, int need1, hipStream_t s) {
-    if (g <= kFuseMaxBlocks)
-        hipLaunchKernelGGL((k_sc2_round<FOLD, true>), dim3(g), dim3(kThreads), 0, s, Min, Zin, Mout, Zout, r, half, partial,
-                           ticket, result3, need1);
-    else
-        hipLaunchKernelGGL((k_sc2_round<FOLD, false>), dim3(g), dim3(kThreads), 0, s, Min, Zin, Mout, Zout, r, half,
-                           partial, ticket, result3, need1);
-}
 
-template <bool FOLD, bool NEED1>
-static void sc1_wave_launch(int g, const Tables3& in, const Tables3& out, const Fr* Ein, Fr* Eout, const Fr& r,
-                            uint64_t half, Fr* partial, uint32_t* ticket, Fr* result3, hipStream_t s) {
-    if (g <= kFuseMaxBlocks)
-        hipLaunchKernelGGL((k_sc1_wave<FOLD, NEED1, true>), dim3(g), dim3(kThreads), 0, s, in, out, Ein, Eout, r, half,
-                           partial, ticket, result3);
-    else
-        hipLaunchKernelGGL((k_sc1_wave<FOLD, NEED1, false>), dim3(g), dim3(kThreads), 0, s, in, out, Ein, Eout, r, half,
-                           partial, ticket, result3);
-}
-template <bool FOLD, bool NEED1>
-static void sc2_wave_launch(int g, const Fr* Min, const Fr* Zin, Fr* Mout, Fr* Zout, const Fr& r, uint64_t half,
-                            Fr* partial, uint32_t* ticket, Fr* result3, hipStream_t s) {
-    if (g <= kFuseMaxBlocks)
-        hipLaunchKernelGGL((k_sc2_wave<FOLD, NEED1, true>), dim3(g), dim3(kThreads), 0, s, Min, Zin, Mout, Zout, r, half,
-                           partial, ticket, result3);
-    else
-        hipLaunchKernelGGL((k_sc2_wave<FOLD, NEED1, false>), dim3(g), dim3(kThreads), 0, s, Min, Zin, Mout, Zout, r,
-                           half, partial, ticket, result3);
-}
-
-void launch_sc1_round(bool fold, const Tables3& in, const Tables3& out, const Fr* Ein, Fr* Eout, const Fr& r,
-                      uint64_t half, Fr* partial, uint32_t* ticket, Fr* result3, bool need1, hipStream_t s) {
-    int g = sc_grid(half);
-    kp_begin(KP_SC1, s);
+RoundPlan sc_round_plan(int which, int k, bool fold, bool need1, uint64_t half) {
+    RoundPlan p{};
     if (half >= kWaveMinHalf) {
-        g = grid_for(half, kWaveMaxBlocks);
-        if (fold && need1)
-            sc1_wave_launch<true, true>(g, in, out, Ein, Eout, r, half, partial, ticket, result3, s);
-        else if (fold)
-            sc1_wave_launch<true, false>(g, in, out, Ein, Eout, r, half, partial, ticket, result3, s);
-        else if (need1)
-            sc1_wave_launch<false, true>(g, in, out, Ein, Eout, r, half, partial, ticket, result3, s);
-        else
-            sc1_wave_launch<false, false>(g, in, out, Ein, Eout, r, half, partial, ticket, result3, s);
-    } else if (fold && !need1) {  // small fold round: quad per pair, last-block reduction
-        g = grid_for(4 * half, kFuseMaxBlocks);
-        hipLaunchKernelGGL(k_sc1_fold_quad<true>, dim3(g), dim3(kThreads), 0, s, in, out, Ein, Eout, r, half, partial,
-                           ticket, result3);
-    } else if (fold)
-        sc1_launch<true>(g, in, out, Ein, Eout, r, half, partial, ticket, result3, need1 ? 1 : 0, s);
-    else
-        sc1_launch<false>(g, in, out, Ein, Eout, r, half, partial, ticket, result3, need1 ? 1 : 0, s);
-    // algorithmic bytes: fold reads 4 Fr x 3 tables + 2 E, writes 2 x 3 + 1 E; no fold reads 2 x 3 + 1
-    kp_end(32.0 * (double)half * (fold ? (14.0 + 6.0 + (Eout ? 1.0 : 0.0)) : 7.0), s);
-    if (g > kFuseMaxBlocks) hipLaunchKernelGGL(k_reduce_partials<3>, dim3(1), dim3(kThreads), 0, s, partial, g, result3);
+        p.form = kRoundWave;
+        p.grid = grid_for(half, kWaveMaxBlocks);
+    } else if (fold && !need1) {  // small fold round: a quad (sumcheck 1) or a lane pair (2) per pair
+        p.form = kRoundSplit;
+        p.grid = grid_for((which == 1 ? 4 : 2) * half, kFuseMaxBlocks);
+    } else {  // small rounds that need G(1) / P(1), and a small round 1: a lane per pair
+        p.form = kRoundLane;
+        p.grid = sc_grid(half);
+    }
+    p.fused = p.grid <= kFuseMaxBlocks;
+    p.per_proof = k == 1 || p.form == kRoundLane;  // the lane form has no group kernel
+    return p;
 }
 
-void launch_sc2_round(bool fold, const Fr* Min, const Fr* Zin, Fr* Mout, Fr* Zout, const Fr& r, uint64_t half,
-                      Fr* partial, uint32_t* ticket, Fr* result3, bool need1, hipStream_t s) {
-    int g = sc_grid(half);
-    kp_begin(KP_SC2, s);
-    if (half >= kWaveMinHalf) {
-        g = grid_for(half, kWaveMaxBlocks);
-        if (fold && need1)
-            sc2_wave_launch<true, true>(g, Min, Zin, Mout, Zout, r, half, partial, ticket, result3, s);
-        else if (fold)
-            sc2_wave_launch<true, false>(g, Min, Zin, Mout, Zout, r, half, partial, ticket, result3, s);
-        else if (need1)
-            sc2_wave_launch<false, true>(g, Min, Zin, Mout, Zout, r, half, partial, ticket, result3, s);
-        else
-            sc2_wave_launch<false, false>(g, Min, Zin, Mout, Zout, r, half, partial, ticket, result3, s);
-    } else if (fold && !need1) {  // small fold round: lane pair per pair
-        g = grid_for(2 * half, kFuseMaxBlocks);
-        hipLaunchKernelGGL(k_sc2_fold_pair<true>, dim3(g), dim3(kThreads), 0, s, Min, Zin, Mout, Zout, r, half, partial,
-                           ticket, result3);
-    } else if (fold)
-        sc2_launch<true>(g, Min, Zin, Mout, Zout, r, half, partial, ticket, result3, need1 ? 1 : 0, s);
+// the round's kernel for one proof, and for the k proofs of a group (wave and split forms)
+static void round_kernel(const RoundPlan& p, bool fold, bool need1, uint64_t half, const Sc1Job& j, hipStream_t s) {
+    const dim3 g(p.grid), b(kThreads);
+    if (p.form == kRoundWave)
+        with_bool(fold, [&](auto F) {
+            with_bool(need1, [&](auto N) {
+                with_bool(p.fused, [&](auto U) {
+                    hipLaunchKernelGGL((k_sc1_wave<SPX_BV(F), SPX_BV(N), SPX_BV(U)>), g, b, 0, s, j.in, j.out, j.Ein, j.Eout,
+                                       j.r, half, j.partial, j.ticket, j.result3);
+                });
+            });
+        });
+    else if (p.form == kRoundSplit)
+        hipLaunchKernelGGL(k_sc1_fold_quad<true>, g, b, 0, s, j.in, j.out, j.Ein, j.Eout, j.r, half, j.partial, j.ticket,
+                           j.result3);
     else
-        sc2_launch<false>(g, Min, Zin, Mout, Zout, r, half, partial, ticket, result3, need1 ? 1 : 0, s);
-    kp_end(32.0 * (double)half * (fold ? 12.0 : 4.0), s);
-    if (g > kFuseMaxBlocks) hipLaunchKernelGGL(k_reduce_partials<3>, dim3(1), dim3(kThreads), 0, s, partial, g, result3);
+        with_bool(fold, [&](auto F) {
+            with_bool(p.fused, [&](auto U) {
+                hipLaunchKernelGGL((k_sc1_round<SPX_BV(F), SPX_BV(U)>), g, b, 0, s, j.in, j.out, j.Ein, j.Eout, j.r, half,
+                                   j.partial, j.ticket, j.result3, need1 ? 1 : 0);
+            });
+        });
 }
+static void round_kernel(const RoundPlan& p, bool fold, bool need1, uint64_t half, const Sc2Job& j, hipStream_t s) {
+    const dim3 g(p.grid), b(kThreads);
+    if (p.form == kRoundWave)
+        with_bool(fold, [&](auto F) {
+            with_bool(need1, [&](auto N) {
+                with_bool(p.fused, [&](auto U) {
+                    hipLaunchKernelGGL((k_sc2_wave<SPX_BV(F), SPX_BV(N), SPX_BV(U)>), g, b, 0, s, j.Min, j.Zin, j.Mout, j.Zout,
+                                       j.r, half, j.partial, j.ticket, j.result3);
+                });
+            });
+        });
+    else if (p.form == kRoundSplit)
+        hipLaunchKernelGGL(k_sc2_fold_pair<true>, g, b, 0, s, j.Min, j.Zin, j.Mout, j.Zout, j.r, half, j.partial, j.ticket,
+                           j.result3);
+    else
+        with_bool(fold, [&](auto F) {
+            with_bool(p.fused, [&](auto U) {
+                hipLaunchKernelGGL((k_sc2_round<SPX_BV(F), SPX_BV(U)>), g, b, 0, s, j.Min, j.Zin, j.Mout, j.Zout, j.r, half,
+                                   j.partial, j.ticket, j.result3, need1 ? 1 : 0);
+            });
+        });
+}
+static void round_kernel_group(const RoundPlan& p, bool fold, bool need1, uint64_t half, int k, const Sc1Group& G,
+                               hipStream_t s) {
+    const dim3 g(p.grid, k), b(kThreads);
+    if (p.form == kRoundSplit) {
+        hipLaunchKernelGGL(k_sc1_fold_quad_group, g, b, 0, s, G, half);
+        return;
+    }
+    with_bool(fold, [&](auto F) {
+        with_bool(need1, [&](auto N) {
+            with_bool(p.fused, [&](auto U) {
+                hipLaunchKernelGGL((k_sc1_wave_group<SPX_BV(F), SPX_BV(N), SPX_BV(U)>), g, b, 0, s, G, half);
+            });
+        });
+    });
+}
+static void round_kernel_group(const RoundPlan& p, bool fold, bool need1, uint64_t half, int k, const Sc2Group& G,
+                               hipStream_t s) {
+    const dim3 g(p.grid, k), b(kThreads);
+    if (p.form == kRoundSplit) {
+        hipLaunchKernelGGL(k_sc2_fold_pair_group, g, b, 0, s, G, half);
+        return;
+    }
+    with_bool(fold, [&](auto F) {
+        with_bool(need1, [&](auto N) {
+            with_bool(p.fused, [&](auto U) {
+                hipLaunchKernelGGL((k_sc2_wave_group<SPX_BV(F), SPX_BV(N), SPX_BV(U)>), g, b, 0, s, G, half);
+            });
+        });
+    });
+}
+// algorithmic Fr per pair. Sumcheck 1: a fold reads 4 Fr x 3 tables + 2 E and writes 2 x 3 + 1 E, no fold
+// reads 2 x 3 + 1; sumcheck 2: two tables
+static double round_fr(const Sc1Job& j, bool fold) { return fold ? 14.0 + 6.0 + (j.Eout ? 1.0 : 0.0) : 7.0; }
+static double round_fr(const Sc2Job&, bool fold) { return fold ? 12.0 : 4.0; }
 
-// ---- lockstep groups: the launch decisions of launch_sc1_round / launch_sc2_round, one launch for k
-// proofs (grid gridDim.x per proof, blockIdx.y = proof). Round shapes without a group kernel (small
-// rounds that need G(1), or a round 1 below kWaveMinHalf) launch per proof.
 template <class Group, class Job>
-static Group group_of(int k, const Job* jobs) {
-    if (k < 1 || k > kGroupMax) throw std::invalid_argument("lockstep group size out of range");
-    Group g{};
-    for (int i = 0; i < k; ++i) g.j[i] = jobs[i];
-    return g;
-}
-template <bool FOLD, bool NEED1>
-static void sc1_wave_group_launch(int k, int g, const Sc1Group& G, uint64_t half, hipStream_t s) {
-    if (g <= kFuseMaxBlocks)
-        hipLaunchKernelGGL((k_sc1_wave_group<FOLD, NEED1, true>), dim3(g, k), dim3(kThreads), 0, s, G, half);
-    else
-        hipLaunchKernelGGL((k_sc1_wave_group<FOLD, NEED1, false>), dim3(g, k), dim3(kThreads), 0, s, G, half);
-}
-template <bool FOLD, bool NEED1>
-static void sc2_wave_group_launch(int k, int g, const Sc2Group& G, uint64_t half, hipStream_t s) {
-    if (g <= kFuseMaxBlocks)
-        hipLaunchKernelGGL((k_sc2_wave_group<FOLD, NEED1, true>), dim3(g, k), dim3(kThreads), 0, s, G, half);
-    else
-        hipLaunchKernelGGL((k_sc2_wave_group<FOLD, NEED1, false>), dim3(g, k), dim3(kThreads), 0, s, G, half);
-}
-void launch_sc1_round_group(int k, bool fold, const Sc1Job* jobs, uint64_t half, bool need1, hipStream_t s) {
-    const Sc1Group G = group_of<Sc1Group>(k, jobs);
-    if (half < kWaveMinHalf && !(fold && !need1)) {
-        for (int i = 0; i < k; ++i)
-            launch_sc1_round(fold, jobs[i].in, jobs[i].out, jobs[i].Ein, jobs[i].Eout, jobs[i].r, half, jobs[i].partial,
-                             jobs[i].ticket, jobs[i].result3, need1, s);
+static void launch_round(int which, int k, const Job* jobs, bool fold, bool need1, uint64_t half, hipStream_t s) {
+    check_group(k);
+    const RoundPlan p = sc_round_plan(which, k, fold, need1, half);
+    const int id = which == 1 ? KP_SC1 : KP_SC2;
+    if (p.per_proof) {
+        for (int i = 0; i < k; ++i) {
+            kp_begin(id, s);
+            round_kernel(p, fold, need1, half, jobs[i], s);
+            kp_end(32.0 * (double)half * round_fr(jobs[i], fold), s);
+            if (!p.fused)
+                hipLaunchKernelGGL(k_reduce_partials<3>, dim3(1), dim3(kThreads), 0, s, jobs[i].partial, p.grid,
+                                   jobs[i].result3);
+        }
         return;
     }
-    int g;
-    kp_begin(KP_SC1, s);
-    if (half >= kWaveMinHalf) {
-        g = grid_for(half, kWaveMaxBlocks);
-        if (fold && need1)
-            sc1_wave_group_launch<true, true>(k, g, G, half, s);
-        else if (fold)
-            sc1_wave_group_launch<true, false>(k, g, G, half, s);
-        else if (need1)
-            sc1_wave_group_launch<false, true>(k, g, G, half, s);
-        else
-            sc1_wave_group_launch<false, false>(k, g, G, half, s);
-    } else {  // small fold round without G(1)
-        g = grid_for(4 * half, kFuseMaxBlocks);
-        hipLaunchKernelGGL(k_sc1_fold_quad_group, dim3(g, k), dim3(kThreads), 0, s, G, half);
-    }
-    kp_end(32.0 * (double)k * (double)half * (fold ? (14.0 + 6.0 + (jobs[0].Eout ? 1.0 : 0.0)) : 7.0), s);
-    if (g > kFuseMaxBlocks)
-        hipLaunchKernelGGL(k_reduce_partials_group<Sc1Group>, dim3(k), dim3(kThreads), 0, s, G, g);
+    const Group G = group_of<Group>(k, jobs);
+    kp_begin(id, s);
+    round_kernel_group(p, fold, need1, half, k, G, s);
+    kp_end(32.0 * (double)k * (double)half * round_fr(jobs[0], fold), s);
+    if (!p.fused) hipLaunchKernelGGL(k_reduce_partials_group<Group>, dim3(k), dim3(kThreads), 0, s, G, p.grid);
 }
-void launch_sc2_round_group(int k, bool fold, const Sc2Job* jobs, uint64_t half, bool need1, hipStream_t s) {
-    const Sc2Group G = group_of<Sc2Group>(k, jobs);
-    if (half < kWaveMinHalf && !(fold && !need1)) {
-        for (int i = 0; i < k; ++i)
-            launch_sc2_round(fold, jobs[i].Min, jobs[i].Zin, jobs[i].Mout, jobs[i].Zout, jobs[i].r, half, jobs[i].partial,
-                             jobs[i].ticket, jobs[i].result3, need1, s);
-        return;
-    }
-    int g;
-    kp_begin(KP_SC2, s);
-    if (half >= kWaveMinHalf) {
-        g = grid_for(half, kWaveMaxBlocks);
-        if (fold && need1)
-            sc2_wave_group_launch<true, true>(k, g, G, half, s);
-        else if (fold)
-            sc2_wave_group_launch<true, false>(k, g, G, half, s);
-        else if (need1)
-            sc2_wave_group_launch<false, true>(k, g, G, half, s);
-        else
-            sc2_wave_group_launch<false, false>(k, g, G, half, s);
-    } else {  // small fold round without P(1)
-        g = grid_for(2 * half, kFuseMaxBlocks);
-        hipLaunchKernelGGL(k_sc2_fold_pair_group, dim3(g, k), dim3(kThreads), 0, s, G, half);
-    }
-    kp_end(32.0 * (double)k * (double)half * (fold ? 12.0 : 4.0), s);
-    if (g > kFuseMaxBlocks)
-        hipLaunchKernelGGL(k_reduce_partials_group<Sc2Group>, dim3(k), dim3(kThreads), 0, s, G, g);
+void launch_sc1_round(int k, const Sc1Job* jobs, bool fold, bool need1, uint64_t half, hipStream_t s) {
+    launch_round<Sc1Group>(1, k, jobs, fold, need1, half, s);
+}
+void launch_sc2_round(int k, const Sc2Job* jobs, bool fold, bool need1, uint64_t half, hipStream_t s) {
+    launch_round<Sc2Group>(2, k, jobs, fold, need1, half, s);
 }
 
-// ---- the other steps of a lockstep group (prove_group), one launch per step for the k proofs
-template <class J>
-static GroupOf<J> group_check(int k) {
-    if (k < 1 || k > kGroupMax) throw std::invalid_argument("lockstep group size out of range");
-    return GroupOf<J>{};
-}
-void launch_spmv_sliced_group(int k, const SpmvSlicedView& v, const Fr* const* z, const Tables3* out, uint64_t entries,
-                              hipStream_t s) {
-    GroupOf<SpmvJob> g = group_check<SpmvJob>(k);
-    for (int i = 0; i < k; ++i) g.j[i] = SpmvJob{z[i], {out[i].t[0], out[i].t[1], out[i].t[2]}};
-    const uint64_t per_xcd = (entries / 8 + kThreads * kSpmvPer - 1) / (kThreads * kSpmvPer);
-    // k proofs per entry: as many workgroups as one proof's launch has, each doing k proofs' products
-    const uint32_t Q = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, per_xcd));
-    hipLaunchKernelGGL(k_spmv_sliced_group, dim3(8 * Q), dim3(kThreads), 0, s, v, g, k, entries);
-}
-void launch_eq_table_group(int k, const Fr* const* r_dev, int nvar, uint64_t base, uint64_t count, Fr* const* out,
-                           Fr* const* lo, Fr* const* hi, hipStream_t s) {
-    const int klo = (nvar + 1) / 2, khi = nvar - klo;
-    if (nvar < 0 || klo > 13) throw std::invalid_argument("launch_eq_table_group: more than 26 variables");
-    GroupOf<EqfJob> gf = group_check<EqfJob>(k);
-    GroupOf<EqxJob> gx = group_check<EqxJob>(k);
-    for (int i = 0; i < k; ++i) {
-        EqFactors ef{};
-        ef.nf = 2;
-        ef.k[0] = klo;
-        ef.k[1] = khi;
-        ef.t[0] = lo[i];
-        ef.t[1] = hi[i];
-        gf.j[i] = EqfJob{r_dev[i], ef, nullptr};
-        gx.j[i] = EqxJob{lo[i], hi[i], out[i]};
-    }
-    hipLaunchKernelGGL(k_eq_factors_group, dim3(2, k), dim3(kEqThreads), 0, s, gf);
-    kp_begin(KP_EQ, s);
-    hipLaunchKernelGGL(k_eq_expand_group, dim3(grid_for(count, 8192), k), dim3(kThreads), 0, s, gx, klo, base, count);
-    kp_end(32.0 * (double)count * k, s);
-}
-void launch_col_stream_group(int k, const ColStreamView& cv, const Fr* const* r_x, int L, const Fr* const* scale,
-                             Fr* const* out, Fr* const* eq_scratch, hipStream_t s) {
-    GroupOf<EqfJob> gf = group_check<EqfJob>(k);
-    GroupOf<ColJob> gc = group_check<ColJob>(k);
-    int nf = 0;
-    for (int i = 0; i < k; ++i) {
-        const EqFactors ef = eq_factors_for(L, eq_scratch[i]);
-        nf = ef.nf;
-        gf.j[i] = EqfJob{r_x[i], ef, scale[i]};
-        gc.j[i] = ColJob{ef, out[i]};
-    }
-    hipLaunchKernelGGL(k_eq_factors_group, dim3(nf, k), dim3(kEqThreads), 0, s, gf);
-    if (cv.nslices) {
-        const uint32_t nwin = (cv.nslices + kColWindow - 1) / kColWindow;
-        hipLaunchKernelGGL(k_col_stream_group, dim3(nwin, k), dim3(kThreads), 0, s, cv, gc);
-    }
-}
-void launch_open_eval_group(int k, const Fr* const* z, Fr* const* bufA, Fr* const* bufB, const Fr* points, int L,
-                            uint64_t n, Fr* const* last, hipStream_t s) {
-    group_check<LevelJob>(k);
-    std::vector<const Fr*> rin(z, z + k);
-    kp_begin(KP_OPEN, s);
-    bool tail = false;
-    int nb = 0;
+// The stubbed opening's chain: three levels per launch while the table is large, then the tail in one
+// launch, as soon as it takes every remaining level. (open_z's quotient chain has its own rule for the
+// levels per fold: it stops in front of the tail, so that the tail writes quotients.)
+static bool open_fold_wave(uint64_t nout) { return nout >= kWaveMinHalf; }  // whole waves of 64 outputs
+OpenEvalPlan open_eval_plan(int L) {
+    OpenEvalPlan pl{{}, true};
     for (int i = 0; i < L;) {
-        Fr* const* rout = (nb++ & 1) ? bufB : bufA;
-        const uint64_t half = n >> (i + 1);
-        if (open_tail_levels(half, L - i) == L - i) {  // the remaining levels, straight into `last`
-            for (int j0 = 0; j0 < k; j0 += kTailGroup) {
-                const int kk = std::min(kTailGroup, k - j0);
-                GroupOf<TailJob, kTailGroup> g{};
-                for (int j = 0; j < kk; ++j) {
-                    g.j[j].rin = rin[j0 + j];
-                    g.j[j].last = last[j0 + j];
-                    for (int q = i; q < L; ++q) g.j[j].pts.p[q - i] = points[(size_t)(j0 + j) * L + q];
-                }
-                hipLaunchKernelGGL(k_open_tail_group, dim3(1, kk), dim3(kTailMax), 0, s, g, (uint32_t)half, L - i);
-            }
-            tail = true;
+        const uint64_t half = (1ull << L) >> (i + 1);
+        if (open_tail_levels(half, L - i) == L - i) {
+            pl.steps.push_back(OpenStep{kOpenTail, i, L - i, half, false});
+            pl.copy = false;
             break;
         }
         const int nf = L - i >= 3 && (half >> 2) >= 1 ? 3 : (L - i >= 2 && (half >> 1) >= 1 ? 2 : 1);
-        const uint64_t nout = n >> (i + nf);
-        if (nf == 3 || nf == 2) {
-            auto run = [&](auto tag) {
-                constexpr int NF = decltype(tag)::value;
-                GroupOf<FoldJob<NF>> g{};
-                for (int j = 0; j < k; ++j) {
-                    g.j[j].rin = rin[j];
-                    g.j[j].rout = rout[j];
-                    for (int q = 0; q < NF; ++q) g.j[j].a.p[q] = points[(size_t)j * L + i + q], g.j[j].a.qoff[q] = ~0ull;
-                }
-                if (nout >= kWaveMinHalf)
-                    hipLaunchKernelGGL(k_open_fold_wave_group<NF>, dim3(grid_for(nout, 8192), k), dim3(kThreads), 0, s, g,
-                                       nout);
-                else
-                    hipLaunchKernelGGL(k_open_fold_group<NF>, dim3(grid_for(nout, 8192), k), dim3(kThreads), 0, s, g, nout);
-            };
-            if (nf == 3)
-                run(std::integral_constant<int, 3>{});
-            else
-                run(std::integral_constant<int, 2>{});
-        } else {
-            GroupOf<LevelJob> g{};
-            for (int j = 0; j < k; ++j) g.j[j] = LevelJob{rin[j], rout[j], points[(size_t)j * L + i]};
-            hipLaunchKernelGGL(k_open_level_group, dim3(grid_for(half, 8192), k), dim3(kThreads), 0, s, g, half);
-        }
-        for (int j = 0; j < k; ++j) rin[j] = rout[j];
+        const uint64_t nout = (1ull << L) >> (i + nf);
+        if (nf >= 2)
+            pl.steps.push_back(OpenStep{kOpenFold, i, nf, nout, open_fold_wave(nout)});
+        else
+            pl.steps.push_back(OpenStep{kOpenLevel, i, 1, half, false});
         i += nf;
     }
-    kp_end(32.0 * 2.0 * (double)n * k, s);  // reads ~2n over the levels, writes ~n
-    if (!tail) {  // the chain ended on a fold: its one-entry table to `last`
-        GroupOf<CopyJob> g{};
-        for (int j = 0; j < k; ++j) g.j[j] = CopyJob{{rin[j], nullptr, nullptr}, last[j]};
-        hipLaunchKernelGGL(k_copy_runs_group, dim3(k), dim3(64), 0, s, g, 1, 1);
+    return pl;
+}
+// one step for the k proofs of a group in one launch (a tail: at most kTailGroup proofs per launch)
+static void open_step_group(const OpenStep& st, int k, const OpenEvalJob* jobs, const Fr* const* rin, Fr* const* rout,
+                            hipStream_t s) {
+    if (st.kind == kOpenTail) {
+        for (int j0 = 0; j0 < k; j0 += kTailGroup) {
+            const int kk = std::min(kTailGroup, k - j0);
+            GroupOf<TailJob, kTailGroup> g{};
+            for (int j = 0; j < kk; ++j) {
+                g.j[j].rin = rin[j0 + j];
+                g.j[j].last = jobs[j0 + j].last ? jobs[j0 + j].last : rout[j0 + j];
+                for (int q = 0; q < st.levels; ++q) g.j[j].pts.p[q] = jobs[j0 + j].points[st.first + q];
+            }
+            hipLaunchKernelGGL(k_open_tail_group, dim3(1, kk), dim3(kTailMax), 0, s, g, (uint32_t)st.size, st.levels);
+        }
+    } else if (st.kind == kOpenFold) {
+        const dim3 grid(grid_for(st.size, 8192), k), b(kThreads);
+        auto run = [&](auto tag) {
+            constexpr int NF = decltype(tag)::value;
+            GroupOf<FoldJob<NF>> g{};
+            for (int j = 0; j < k; ++j) {
+                g.j[j].rin = rin[j];
+                g.j[j].rout = rout[j];
+                for (int q = 0; q < NF; ++q) g.j[j].a.p[q] = jobs[j].points[st.first + q], g.j[j].a.qoff[q] = ~0ull;
+            }
+            if (st.wave)
+                hipLaunchKernelGGL(k_open_fold_wave_group<NF>, grid, b, 0, s, g, st.size);
+            else
+                hipLaunchKernelGGL(k_open_fold_group<NF>, grid, b, 0, s, g, st.size);
+        };
+        if (st.levels == 3)
+            run(std::integral_constant<int, 3>{});
+        else
+            run(std::integral_constant<int, 2>{});
+    } else {
+        GroupOf<LevelJob> g{};
+        for (int j = 0; j < k; ++j) g.j[j] = LevelJob{rin[j], rout[j], jobs[j].points[st.first]};
+        hipLaunchKernelGGL(k_open_level_group, dim3(grid_for(st.size, 8192), k), dim3(kThreads), 0, s, g, st.size);
     }
 }
-void launch_copy_runs_group(int k, const Tables3* src, int nruns, int per, Fr* const* dst, hipStream_t s) {
-    GroupOf<CopyJob> g = group_check<CopyJob>(k);
-    if (nruns < 1 || nruns > 3 || per < 1 || nruns * per > 4096) throw std::invalid_argument("launch_copy_runs_group");
-    for (int j = 0; j < k; ++j) g.j[j] = CopyJob{{src[j].t[0], src[j].t[1], src[j].t[2]}, dst[j]};
+// step n of a job's chain writes its buffer n & 1; the value ends in `last`, or without one where the
+// last step leaves it (z itself for a table of one entry)
+static Fr* open_step_out(const OpenEvalJob& j, size_t n) { return (n & 1) ? j.bufB : j.bufA; }
+const Fr* open_eval_result(const OpenEvalJob& job, int L) {
+    const size_t n = open_eval_plan(L).steps.size();
+    return job.last ? job.last : (n ? open_step_out(job, n - 1) : job.z);
+}
+void launch_open_eval(int k, const OpenEvalJob* jobs, int L, hipStream_t s) {
+    check_group(k);
+    const OpenEvalPlan pl = open_eval_plan(L);
+    const Fr* rin[kGroupMax];
+    Fr* rout[kGroupMax];
+    for (int j = 0; j < k; ++j) rin[j] = jobs[j].z;
+    if (k > 1) kp_begin(KP_OPEN, s);  // (one proof: the per-step launchers record their own)
+    for (size_t n = 0; n < pl.steps.size(); ++n) {
+        const OpenStep& st = pl.steps[n];
+        for (int j = 0; j < k; ++j) rout[j] = open_step_out(jobs[j], n);
+        if (k > 1) {
+            open_step_group(st, k, jobs, rin, rout, s);
+        } else if (st.kind == kOpenTail) {
+            launch_open_tail(rin[0], nullptr, st.size, st.levels, jobs[0].points + st.first,
+                             jobs[0].last ? jobs[0].last : rout[0], s);
+        } else if (st.kind == kOpenFold) {
+            const uint64_t qoffs[3] = {~0ull, ~0ull, ~0ull};
+            launch_open_fold(rin[0], rout[0], nullptr, st.levels, jobs[0].points + st.first, qoffs, st.size, s);
+        } else {
+            launch_open_level(rin[0], rout[0], nullptr, jobs[0].points[st.first], st.size, s);
+        }
+        for (int j = 0; j < k; ++j) rin[j] = rout[j];
+    }
+    if (k > 1) kp_end(32.0 * 2.0 * (double)(1ull << L) * k, s);  // reads ~2n over the levels, writes ~n
+    if (!pl.copy) return;
+    // the chain ended on a fold: its one-entry table to `last`, for the jobs that name one
+    GroupOf<CopyJob> g{};
+    int nc = 0;
+    for (int j = 0; j < k; ++j)
+        if (jobs[j].last) g.j[nc++] = CopyJob{{rin[j], nullptr, nullptr}, jobs[j].last};
+    if (nc) hipLaunchKernelGGL(k_copy_runs_group, dim3(nc), dim3(64), 0, s, g, 1, 1);
+}
+void launch_copy_runs(int k, const CopyJob* jobs, int nruns, int per, hipStream_t s) {
+    const GroupOf<CopyJob> g = group_of<GroupOf<CopyJob>>(k, jobs);
+    if (nruns < 1 || nruns > 3 || per < 1 || nruns * per > 4096) throw std::invalid_argument("launch_copy_runs");
     hipLaunchKernelGGL(k_copy_runs_group, dim3(k), dim3(256), 0, s, g, nruns, per);
 }
 
@@ -1841,7 +1827,7 @@ void launch_open_fold(const Fr* rin, Fr* rout, Fr* q, int nf, const Fr* points, 
     const int g = grid_for(nout, 8192);
     double qw = 0;
     for (int j = 0; j < nf; ++j) qw += qoffs[j] != ~0ull ? (double)(nout << (nf - 1 - j)) : 0.0;
-    const bool wave = nout >= kWaveMinHalf;  // whole waves of 64 outputs
+    const bool wave = open_fold_wave(nout);  // (the test that open_eval_plan's steps carry)
     if (nf == 3) {
         FoldArgs<3> a;
         for (int j = 0; j < 3; ++j) a.p[j] = points[j], a.qoff[j] = qoffs[j];
@@ -1870,8 +1856,7 @@ void launch_open_level(const Fr* rin, Fr* rout, Fr* q, const Fr& point, uint64_t
 
 void launch_r1cs_check(int k, const R1csCheckJob* jobs, uint64_t nl, uint64_t row0, hipStream_t s) {
     if (nl < 1) throw std::invalid_argument("witness check of an empty table");
-    GroupOf<R1csCheckJob> g = group_check<R1csCheckJob>(k);
-    for (int i = 0; i < k; ++i) g.j[i] = jobs[i];
+    const GroupOf<R1csCheckJob> g = group_of<GroupOf<R1csCheckJob>>(k, jobs);
     // one row per lane for small tables; from 2^12 rows on four (a quarter of the partials and tickets),
     // and past 2^21 rows whatever kR1csMaxBlocks blocks leave per lane
     const uint64_t per = nl >= 4096 ? 4 : 1;

@@ -381,9 +381,10 @@ std::unique_ptr<PP> pp_generate(Ctx& C, int nv, uint64_t seed) {
     // eq(t[i..], x) scalars for every level (setup.rs:37-60), Montgomery
     DevMem tdev(32 * nv), scal(32 * tot), lo(32 << 14), hi(32 << 14);
     SPX_HIP(hipMemcpyAsync(tdev.p, P->t.data(), 32 * nv, hipMemcpyHostToDevice, C.stream));
-    for (int i = 0; i < nv; ++i)
-        launch_eq_table(tdev.as<Fr>() + i, nv - i, 0, 1ull << (nv - i), scal.as<Fr>() + P->lvl_off[i], lo.as<Fr>(),
-                        hi.as<Fr>(), C.stream);
+    for (int i = 0; i < nv; ++i) {
+        const EqTableJob job{tdev.as<Fr>() + i, scal.as<Fr>() + P->lvl_off[i], lo.as<Fr>(), hi.as<Fr>()};
+        launch_eq_table(1, &job, nv - i, 0, 1ull << (nv - i), C.stream);
+    }
     {
         auto tg = fixed_base_table(P->g);
         DevMem tab(sizeof(G1Aff) * tg.size()), tmp(2 * sizeof(G1Aff) * tot);
@@ -1455,33 +1456,14 @@ static OpenOut open_stub(Ctx& C, const Fr* z_local, int L, const std::vector<HFr
     Fr* bufs[2] = {C.buf<Fr>(Ctx::kSlotOpenA, 32 * std::max<uint64_t>(nl / 2, 1)),
                    C.buf<Fr>(Ctx::kSlotOpenB, 32 * std::max<uint64_t>(nl / 4, 1))};
     uint8_t* h = C.pin_at(Ctx::kPinOpen, 32 * (L + 1), 56 << 10);
-    const Fr* rin = z_local;
     // z(point) only (no quotients): three levels per launch while the table is large, then the tail
-    // in one launch (level by level this was ~L launches per opening: C2's proofs are launch-bound)
-    int nb = 0;
-    for (int i = 0; i < nloc;) {
-        Fr* rout = bufs[nb++ & 1];
-        const uint64_t half = nl >> (i + 1);
-        if (open_tail_levels(half, nloc - i) == nloc - i) {  // the remaining levels in one launch
-            std::vector<Fr> pts(nloc - i);
-            for (int j = i; j < nloc; ++j) pts[j - i] = dev_fr(point[j]);
-            launch_open_tail(rin, nullptr, half, nloc - i, pts.data(), rout, C.stream);
-            rin = rout;
-            break;
-        }
-        const int nf = nloc - i >= 3 && (half >> 2) >= 1 ? 3 : (nloc - i >= 2 && (half >> 1) >= 1 ? 2 : 1);
-        if (nf >= 2) {
-            Fr pts[3];
-            uint64_t qoffs[3] = {~0ull, ~0ull, ~0ull};
-            for (int j = 0; j < nf; ++j) pts[j] = dev_fr(point[i + j]);
-            launch_open_fold(rin, rout, nullptr, nf, pts, qoffs, nl >> (i + nf), C.stream);
-        } else {
-            launch_open_level(rin, rout, nullptr, dev_fr(point[i]), half, C.stream);
-        }
-        rin = rout;
-        i += nf;
-    }
-    SPX_HIP(hipMemcpyAsync(h + 32 * L, rin, 32, hipMemcpyDeviceToHost, C.stream));
+    // in one launch (level by level this was ~L launches per opening: C2's proofs are launch-bound).
+    // The value stays where the chain's last step writes it (no `last`) and is copied from there.
+    std::vector<Fr> pts(std::max(nloc, 1));
+    for (int j = 0; j < nloc; ++j) pts[j] = dev_fr(point[j]);
+    const OpenEvalJob job{z_local, bufs[0], bufs[1], pts.data(), nullptr};
+    launch_open_eval(1, &job, nloc, C.stream);
+    SPX_HIP(hipMemcpyAsync(h + 32 * L, open_eval_result(job, nloc), 32, hipMemcpyDeviceToHost, C.stream));
     C.sync();
     HFr rlast = ld_hfr(h + 32 * L);
     if (G == 1) {
@@ -1551,8 +1533,9 @@ struct UnwindDrain {
 
 // the index's SpMV Az, Bz, Cz of this rank's nl rows: the column-sorted entry list, or CSR rows
 static void launch_rows_spmv(Index& I, const Fr* z, Fr* Az, Fr* Bz, Fr* Cz, Fr* partial, uint64_t nl, hipStream_t s) {
+    const SpmvJob job{z, {Az, Bz, Cz}};
     if (I.rows_sliced.on)
-        launch_spmv_sliced(I.rows_sliced.view(), z, Az, Bz, Cz, I.rows_sliced.entries, s);
+        launch_spmv_sliced(1, &job, I.rows_sliced.view(), I.rows_sliced.entries, s);
     else
         launch_sparse3(0, I.rows.view(), z, Az, Bz, Cz, nullptr, nl, I.rows.chunks.as<LongChunk>(), I.rows.nchunks,
                        I.rows.lrows.as<LongRow>(), I.rows.nlrows, partial, s);
@@ -1592,7 +1575,49 @@ struct ProofScratch {
         take(64);  // slack
         return off;
     }
+
+    // The sumchecks' device rounds. Round i (1-based) reads the running tables; from round 2 on it first
+    // binds the previous challenge into the ping-pong buffers of its parity, which become the running
+    // tables (done_round). The rounds' sums land in res_dev (host-mapped pinned memory).
+    Tables3 cur{};
+    const Fr *Ecur = nullptr, *Mc = nullptr, *Zc = nullptr;
+    uint32_t* ticket = nullptr;
+    Fr* res_dev = nullptr;
+    void begin1() { cur = Tables3{{Az, Bz, Cz}}, Ecur = E1; }
+    void begin2(const Fr* z_local) { Mc = M0, Zc = z_local; }
+    // (nvars local variables: the last round's fold writes no E, nothing reads it)
+    Sc1Job sc1_job(int i, int nvars, const std::vector<HFr>& r) const {
+        Sc1Job j{cur, Tables3{{nullptr, nullptr, nullptr}}, Ecur, nullptr, Fr{}, partial, ticket, res_dev};
+        if (i >= 2) {
+            Fr* const* fb = (i % 2 == 0) ? F1 : F2;
+            j.out = Tables3{{fb[0], fb[1], fb[2]}};
+            if (i < nvars) j.Eout = (i & 1) ? Eb : Ea;
+            j.r = dev_fr(r[i - 2]);
+        }
+        return j;
+    }
+    Sc2Job sc2_job(int i, const std::vector<HFr>& r) const {
+        Sc2Job j{Mc, Zc, nullptr, nullptr, Fr{}, partial, ticket, res_dev};
+        if (i >= 2) {
+            j.Mout = (i & 1) ? M2 : M1;
+            j.Zout = (i & 1) ? Z2 : Z1;
+            j.r = dev_fr(r[i - 2]);
+        }
+        return j;
+    }
+    void done_round(const Sc1Job& j) {
+        if (j.out.t[0]) cur = j.out;
+        if (j.Eout) Ecur = j.Eout;
+    }
+    void done_round(const Sc2Job& j) {
+        if (j.Mout) Mc = j.Mout, Zc = j.Zout;
+    }
 };
+// a round's G(1) / P(1) is computed on the device if the host cannot derive it from the claim, or checks it
+template <class Sumcheck>
+static bool round_need1(const Sumcheck& sc, bool check) {
+    return check || !sc.derivable();
+}
 
 // round 3's eq table of a 1-variable proof is the constant 1
 static void upload_one(Fr* E1, uint8_t* pin, hipStream_t s) {
@@ -1817,17 +1842,18 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     memcpy(hp, tau.data(), 32 * L);
     SPX_HIP(hipMemcpyAsync(S.chdev, hp, 32 * L, hipMemcpyHostToDevice, C.stream));
     // E_1[b] = eq(tau_1..tau_{L-1}, b) on this rank's block of b
-    if (L >= 2)
-        launch_eq_table(S.chdev + 1, L - 1, (uint64_t)rank * (nl / 2), nl / 2, S.E1, S.eqlo, S.eqhi, C.stream);
-    else
+    if (L >= 2) {
+        const EqTableJob job{S.chdev + 1, S.E1, S.eqlo, S.eqhi};
+        launch_eq_table(1, &job, L - 1, (uint64_t)rank * (nl / 2), nl / 2, C.stream);
+    } else {
         upload_one(S.E1, hp + 4096, C.stream);
+    }
     // ---- sumcheck #1 (lib.rs:86-103)
     io.sumcheck_header(L + 2, L);
     Sumcheck1 s1(io, std::move(tau));
-    Fr* res_dev = C.pin_dev<Fr>(hp);  // the rounds' sums land in pinned host memory (hp)
-    Tables3 cur{{S.Az, S.Bz, S.Cz}};
-    const Fr* Ecur = S.E1;
-    Fr* Ebuf[2] = {S.Ea, S.Eb};
+    S.ticket = C.ticket;
+    S.res_dev = C.pin_dev<Fr>(hp);  // the rounds' sums land in pinned host memory (hp)
+    S.begin1();
     // The last ht1 rounds of each sumcheck run on the host, as in prove_group: each rank binds its local
     // tables (<= 64 entries) and, sharded, the ranks' tables are gathered in rank order (the g high
     // variables) before the last g + ht1 rounds. Unsharded: one proof at a time 22.5 vs 22.6 ms
@@ -1837,30 +1863,18 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     const int ht1 = std::max(0, std::min(kGroupHostTail, L - g - 1));
     const uint32_t tn = 2u << ht1;  // entries per table after the device rounds
     for (int i = 1; i <= L - g - ht1; ++i) {
-        const uint64_t half = nl >> i;
-        const bool fold = i >= 2;
-        Tables3 out{{nullptr, nullptr, nullptr}};
-        Fr* Eout = nullptr;
-        if (fold) {
-            Fr** fb = (i % 2 == 0) ? S.F1 : S.F2;
-            out = Tables3{{fb[0], fb[1], fb[2]}};
-            if (i < L - g) Eout = Ebuf[i & 1];
-        }
-        launch_sc1_round(fold, cur, out, Ecur, Eout, fold ? dev_fr(s1.r[i - 2]) : Fr{}, half, partial, C.ticket, res_dev,
-                         !s1.derivable() || check, C.stream);
+        const Sc1Job job = S.sc1_job(i, L - g, s1.r);
+        launch_sc1_round(1, &job, i >= 2, round_need1(s1, check), nl >> i, C.stream);
         C.sync();
         HFr gs[3] = {ld_hfr(hp), ld_hfr(hp + 32), ld_hfr(hp + 64)};
         sum_ranks(comm, gs);
         s1.device_round(gs, check);
-        if (fold) {
-            cur = out;
-            if (Eout) Ecur = Eout;
-        }
+        S.done_round(job);
     }
     // local tables now hold tn entries each (2 when sharded; folded up to r_{L-g-ht1-1}): r_{L-g-ht1} is
     // bound on the host, the ranks' tables are gathered, and the last g + ht1 rounds run there
     for (int m = 0; m < 3; ++m)
-        SPX_HIP(hipMemcpyAsync(hp + 32 * tn * m, cur.t[m], 32 * tn, hipMemcpyDeviceToHost, C.stream));
+        SPX_HIP(hipMemcpyAsync(hp + 32 * tn * m, S.cur.t[m], 32 * tn, hipMemcpyDeviceToHost, C.stream));
     C.sync();
     std::vector<HFr> mine = s1.bind(hp, tn);
     const std::vector<HFr> vabc = s1.tail(rank_order(G == 1 ? std::move(mine) : allgather_fr(comm, mine), 3, G));
@@ -1877,36 +1891,27 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
     SPX_HIP(hipMemcpyAsync(rxdev, hp, 32 * (L + 3), hipMemcpyHostToDevice, C.stream));
     {
         kp_begin(KP_MTV, C.stream);
-        I.cols.launch(rxdev, L, rxdev + L, S.M0, S.eqf, partial, C.stream);
+        const ColStreamJob job{rxdev, rxdev + L, S.M0, S.eqf, partial};
+        I.cols.launch(1, &job, L, C.stream);
         kp_end(I.cols_bytes, C.stream);
     }
     io.sumcheck_header(2, L);
     mark("eval_on_x", tp);
     // ---- sumcheck #2 (lib.rs:114-131)
     Sumcheck2 s2(io, L);
-    const Fr* Mc = S.M0;
-    const Fr* Zc = zl;
-    Fr* Mb[2] = {S.M1, S.M2};
-    Fr* Zb[2] = {S.Z1, S.Z2};
+    S.begin2(zl);
     for (int i = 1; i <= L - g - ht1; ++i) {
-        const uint64_t half = nl >> i;
-        const bool fold = i >= 2;
-        Fr* Mo = fold ? Mb[i & 1] : nullptr;
-        Fr* Zo = fold ? Zb[i & 1] : nullptr;
-        launch_sc2_round(fold, Mc, Zc, Mo, Zo, fold ? dev_fr(s2.r[i - 2]) : Fr{}, half, partial, C.ticket, res_dev,
-                         !s2.derivable() || check, C.stream);
+        const Sc2Job job = S.sc2_job(i, s2.r);
+        launch_sc2_round(1, &job, i >= 2, round_need1(s2, check), nl >> i, C.stream);
         C.sync();
         HFr ps[3] = {ld_hfr(hp), ld_hfr(hp + 32), ld_hfr(hp + 64)};
         sum_ranks(comm, ps);
         s2.device_round(ps, check);
-        if (fold) {
-            Mc = Mo;
-            Zc = Zo;
-        }
+        S.done_round(job);
     }
     if (g + ht1 > 0) {
-        SPX_HIP(hipMemcpyAsync(hp, Mc, 32 * tn, hipMemcpyDeviceToHost, C.stream));
-        SPX_HIP(hipMemcpyAsync(hp + 32 * tn, Zc, 32 * tn, hipMemcpyDeviceToHost, C.stream));
+        SPX_HIP(hipMemcpyAsync(hp, S.Mc, 32 * tn, hipMemcpyDeviceToHost, C.stream));
+        SPX_HIP(hipMemcpyAsync(hp + 32 * tn, S.Zc, 32 * tn, hipMemcpyDeviceToHost, C.stream));
         C.sync();
         mine = s2.bind(hp, tn);
         s2.tail(rank_order(G == 1 ? std::move(mine) : allgather_fr(comm, mine), 2, G));
@@ -1927,7 +1932,7 @@ std::vector<uint8_t> prove(Ctx& C, Index& I, Witness& W, PP* P, const ProveOpts&
 // step. A C2 proof is ~55 small launches and ~40 host waits: with 32 proofs in flight on the context
 // streams' 4 hardware queues the GPU ran ~1 kernel at a time and was idle 65% of the time (trace
 // profiles/r05/r05zg_c2_busy.txt), each proof waiting its turn in a queue. Here the k proofs' sumcheck
-// rounds are one launch each (launch_sc1_round_group: blockIdx.y = proof) with one wait, and the other
+// rounds are one launch each (launch_sc1_round with k jobs: blockIdx.y = proof) with one wait, and the other
 // steps queue the k proofs' launches back to back before one wait. Every value is computed by the same
 // kernels as prove() and by the same host code (sumcheck_host.hpp), so each proof's bytes are its own
 // prove()'s.
@@ -1966,15 +1971,11 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
     uint8_t* stage = C.pin_at(Ctx::kPinStage, (size_t)32 * 8 * L * k, 128 << 10);
     struct P : ProofScratch {
         uint8_t *hp, *ho;
-        Fr* res_dev;
         const Fr* z;
         int log_v;
         ProofStream io;
         Sumcheck1 s1;
         Sumcheck2 s2;
-        Tables3 cur;
-        const Fr* Ecur;
-        const Fr *Mc, *Zc;
     };
     std::vector<P> ps(k);  // (sized once: s1 and s2 point at their proof's io)
     for (int j = 0; j < k; ++j) {
@@ -1983,24 +1984,18 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         p.chdev = chg + (uint64_t)8 * L * j;
         p.hp = hp0 + 8192 * j;
         p.ho = ho0 + 2048 * j;
+        p.ticket = C.ticket + j;
         p.res_dev = C.pin_dev<Fr>(p.hp);
         p.z = Ws[j]->z.as<Fr>();
         p.log_v = ilog2(Ws[j]->v.size() / 32);
         p.io.T = Transcript(os[j].mode == 1, os[j].seed, nullptr);
     }
-    // per-proof pointer arrays for the group launchers
-    auto each = [&](auto f) {
-        using T = decltype(f(ps[0]));
-        std::vector<T> v;
-        for (auto& p : ps) v.push_back(f(p));
-        return v;
-    };
     // ---- SpMV Az, Bz, Cz of every proof (challenge-independent)
     if (I.rows_sliced.on) {
         kp_begin(KP_SPMV, C.stream);
-        const auto zs = each([](P& p) -> const Fr* { return p.z; });
-        const auto outs = each([](P& p) { return Tables3{{p.Az, p.Bz, p.Cz}}; });
-        launch_spmv_sliced_group(k, I.rows_sliced.view(), zs.data(), outs.data(), I.rows_sliced.entries, C.stream);
+        std::vector<SpmvJob> jobs;
+        for (auto& p : ps) jobs.push_back(SpmvJob{p.z, {p.Az, p.Bz, p.Cz}});
+        launch_spmv_sliced(k, jobs.data(), I.rows_sliced.view(), I.rows_sliced.entries, C.stream);
         // one index stream for the group (k_spmv_sliced_group), z and the outputs per proof
         kp_end(I.rows_index_bytes + (I.rows_bytes - I.rows_index_bytes) * k, C.stream);
     } else {
@@ -2035,11 +2030,10 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         std::vector<Fr> flat((size_t)k * L);
         for (int j = 0; j < k; ++j)
             for (int i = 0; i < L; ++i) flat[(size_t)j * L + i] = dev_fr(pts[j][i]);
-        const auto zs = each([](P& p) -> const Fr* { return p.z; });
-        const auto as = each([](P& p) { return p.oA; });
-        const auto bs = each([](P& p) { return p.oB; });
-        const auto last = each([&](P& p) { return C.pin_dev<Fr>(p.ho); });
-        launch_open_eval_group(k, zs.data(), as.data(), bs.data(), flat.data(), L, nl, last.data(), C.stream);
+        std::vector<OpenEvalJob> jobs;
+        for (int j = 0; j < k; ++j)
+            jobs.push_back(OpenEvalJob{ps[j].z, ps[j].oA, ps[j].oB, flat.data() + (size_t)j * L, C.pin_dev<Fr>(ps[j].ho)});
+        launch_open_eval(k, jobs.data(), L, C.stream);
         C.sync();
         const std::vector<Affine<HFq2>> none(L, Affine<HFq2>{HFq2::zero(), HFq2::zero(), true});
         for (auto& p : ps) emit_open(p.io, ld_hfr(p.ho), h_of(nullptr), none);
@@ -2069,17 +2063,14 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
     }
     SPX_HIP(hipMemcpyAsync(chg, stage, (size_t)32 * 8 * L * k, hipMemcpyHostToDevice, C.stream));
     if (L >= 2) {
-        const auto rs = each([](P& p) -> const Fr* { return p.chdev + 1; });
-        const auto outs = each([](P& p) { return p.E1; });
-        const auto lo = each([](P& p) { return p.eqlo; });
-        const auto hi = each([](P& p) { return p.eqhi; });
-        launch_eq_table_group(k, rs.data(), L - 1, 0, nl / 2, outs.data(), lo.data(), hi.data(), C.stream);
+        std::vector<EqTableJob> jobs;
+        for (auto& p : ps) jobs.push_back(EqTableJob{p.chdev + 1, p.E1, p.eqlo, p.eqhi});
+        launch_eq_table(k, jobs.data(), L - 1, 0, nl / 2, C.stream);
     }
     for (auto& p : ps) {
         if (L < 2) upload_one(p.E1, p.hp + 4096, C.stream);
         p.io.sumcheck_header(L + 2, L);
-        p.cur = Tables3{{p.Az, p.Bz, p.Cz}};
-        p.Ecur = p.E1;
+        p.begin1();
     }
     // The last ht rounds of each sumcheck run on the host (the tables are then <= 2^(ht+1) entries: a few
     // microseconds of host arithmetic per round, against a ~30 us launch that holds one of the 4 hardware
@@ -2091,45 +2082,26 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
     // ---- sumcheck 1: one launch and one wait per round for the group
     std::vector<Sc1Job> j1(k);
     for (int i = 1; i <= L - ht; ++i) {
-        const uint64_t half = nl >> i;
-        const bool fold = i >= 2;
-        bool need1 = check;
+        bool need1 = false;  // one flag for the launch: G(1) for all if any proof needs it
         for (int j = 0; j < k; ++j) {
-            P& p = ps[j];
-            Sc1Job& jb = j1[j];
-            jb.in = p.cur;
-            jb.out = Tables3{{nullptr, nullptr, nullptr}};
-            jb.Ein = p.Ecur;
-            jb.Eout = nullptr;
-            if (fold) {
-                Fr** fb = (i % 2 == 0) ? p.F1 : p.F2;
-                jb.out = Tables3{{fb[0], fb[1], fb[2]}};
-                if (i < L) jb.Eout = (i & 1) ? p.Eb : p.Ea;
-            }
-            jb.r = fold ? dev_fr(p.s1.r[i - 2]) : Fr{};
-            jb.partial = p.partial;
-            jb.ticket = C.ticket + j;
-            jb.result3 = p.res_dev;
-            need1 = need1 || !p.s1.derivable();
+            j1[j] = ps[j].sc1_job(i, L, ps[j].s1.r);
+            need1 = need1 || round_need1(ps[j].s1, check);
         }
-        launch_sc1_round_group(k, fold, j1.data(), half, need1, C.stream);
+        launch_sc1_round(k, j1.data(), i >= 2, need1, nl >> i, C.stream);
         C.sync();
         for (int j = 0; j < k; ++j) {
             P& p = ps[j];
             HFr gs[3] = {ld_hfr(p.hp), ld_hfr(p.hp + 32), ld_hfr(p.hp + 64)};
             p.s1.device_round(gs, check);
-            if (fold) {
-                p.cur = j1[j].out;
-                if (j1[j].Eout) p.Ecur = j1[j].Eout;
-            }
+            p.done_round(j1[j]);
         }
     }
     // the tables hold tn = 2^(ht+1) entries each: bind r_{L-ht} on the host, then the host rounds
     const uint32_t tn = 2u << ht;
     {
-        const auto src = each([](P& p) { return p.cur; });
-        const auto dst = each([&](P& p) { return C.pin_dev<Fr>(p.hp); });
-        launch_copy_runs_group(k, src.data(), 3, (int)tn, dst.data(), C.stream);
+        std::vector<CopyJob> jobs;
+        for (auto& p : ps) jobs.push_back(CopyJob{{p.cur.t[0], p.cur.t[1], p.cur.t[2]}, C.pin_dev<Fr>(p.hp)});
+        launch_copy_runs(k, jobs.data(), 3, (int)tn, C.stream);
     }
     C.sync();
     for (int j = 0; j < k; ++j) {
@@ -2146,56 +2118,35 @@ std::vector<std::vector<uint8_t>> prove_group(Ctx& C, Index& I, Witness* const* 
         memcpy(st + 32 * L, rabc, 96);
         p.io.sumcheck_header(2, L);
         p.s2 = Sumcheck2(p.io, L);
-        p.Mc = p.M0;
-        p.Zc = p.z;
+        p.begin2(p.z);
     }
     // ---- round 5: M_rx = sum_m r_m M(r_x, .) of every proof
     SPX_HIP(hipMemcpyAsync(chg, stage, (size_t)32 * 8 * L * k, hipMemcpyHostToDevice, C.stream));
     kp_begin(KP_MTV, C.stream);
-    if (I.cols.longc.nchunks == 0) {
-        const auto rx = each([&](P& p) -> const Fr* { return p.chdev + 2 * L; });
-        const auto sc = each([&](P& p) -> const Fr* { return p.chdev + 3 * L; });
-        const auto outs = each([](P& p) { return p.M0; });
-        const auto eqs = each([](P& p) { return p.eqf; });
-        launch_col_stream_group(k, I.cols.view(), rx.data(), L, sc.data(), outs.data(), eqs.data(), C.stream);
-    } else {
-        for (auto& p : ps) I.cols.launch(p.chdev + 2 * L, L, p.chdev + 3 * L, p.M0, p.eqf, p.partial, C.stream);
+    {
+        std::vector<ColStreamJob> jobs;
+        for (auto& p : ps) jobs.push_back(ColStreamJob{p.chdev + 2 * L, p.chdev + 3 * L, p.M0, p.eqf, p.partial});
+        I.cols.launch(k, jobs.data(), L, C.stream);
     }
     kp_end(I.cols_bytes * k, C.stream);
     // ---- sumcheck 2
     std::vector<Sc2Job> j2(k);
     for (int i = 1; i <= L - ht; ++i) {
-        const uint64_t half = nl >> i;
-        const bool fold = i >= 2;
-        for (int j = 0; j < k; ++j) {
-            P& p = ps[j];
-            Sc2Job& jb = j2[j];
-            jb.Min = p.Mc;
-            jb.Zin = p.Zc;
-            jb.Mout = fold ? ((i & 1) ? p.M2 : p.M1) : nullptr;
-            jb.Zout = fold ? ((i & 1) ? p.Z2 : p.Z1) : nullptr;
-            jb.r = fold ? dev_fr(p.s2.r[i - 2]) : Fr{};
-            jb.partial = p.partial;
-            jb.ticket = C.ticket + j;
-            jb.result3 = p.res_dev;
-        }
-        launch_sc2_round_group(k, fold, j2.data(), half, !fold || check, C.stream);
+        for (int j = 0; j < k; ++j) j2[j] = ps[j].sc2_job(i, ps[j].s2.r);
+        launch_sc2_round(k, j2.data(), i >= 2, round_need1(ps[0].s2, check), nl >> i, C.stream);  // (the same for every proof)
         C.sync();
         for (int j = 0; j < k; ++j) {
             P& p = ps[j];
             HFr q[3] = {ld_hfr(p.hp), ld_hfr(p.hp + 32), ld_hfr(p.hp + 64)};
             p.s2.device_round(q, check);
-            if (fold) {
-                p.Mc = j2[j].Mout;
-                p.Zc = j2[j].Zout;
-            }
+            p.done_round(j2[j]);
         }
     }
     if (ht > 0) {  // M and Z hold tn entries each: bind r_{L-ht}, then the host rounds
         {
-            const auto src = each([](P& p) { return Tables3{{const_cast<Fr*>(p.Mc), const_cast<Fr*>(p.Zc), nullptr}}; });
-            const auto dst = each([&](P& p) { return C.pin_dev<Fr>(p.hp); });
-            launch_copy_runs_group(k, src.data(), 2, (int)tn, dst.data(), C.stream);
+            std::vector<CopyJob> jobs;
+            for (auto& p : ps) jobs.push_back(CopyJob{{p.Mc, p.Zc, nullptr}, C.pin_dev<Fr>(p.hp)});
+            launch_copy_runs(k, jobs.data(), 2, (int)tn, C.stream);
         }
         C.sync();
         for (auto& p : ps) p.s2.tail(p.s2.bind(p.hp, tn));
@@ -2469,7 +2420,8 @@ static HFr eval_matrices_at(Ctx& C, Index& I, const std::vector<HFr>& r_x, const
     uint8_t* hs = C.pin_at(Ctx::kPinStage, 32 * hch.size(), 64 << 10);
     memcpy(hs, hch.data(), 32 * hch.size());
     SPX_HIP(hipMemcpyAsync(ch, hs, 32 * hch.size(), hipMemcpyHostToDevice, C.stream));
-    I.cols.launch(ch, L, ch + L, M0, eqf, partial, C.stream);
+    const ColStreamJob cjob{ch, ch + L, M0, eqf, partial};
+    I.cols.launch(1, &cjob, L, C.stream);
     // fold at r_y (variable 0 = LSB): M0 -> EQ (as q scratch) / Mb ping-pong
     const Fr* rin = M0;
     Fr* bufs[2] = {Mb, M0};
@@ -3252,8 +3204,9 @@ std::vector<uint8_t> k_sum_over_y(Ctx& C, const HostCsr& m, const uint8_t* z) {
     launch_to_mont(zd.as<Fr>(), n, err.as<int>(), C.stream);
     Fr* o = out.as<Fr>();
     if (D.nchunks > (int)4096) part.alloc(32 * D.nchunks);
+    const SpmvJob sjob{zd.as<Fr>(), {o, o + n, o + 2 * n}};
     if (S.on)
-        launch_spmv_sliced(S.view(), zd.as<Fr>(), o, o + n, o + 2 * n, S.entries, C.stream);
+        launch_spmv_sliced(1, &sjob, S.view(), S.entries, C.stream);
     else
         launch_sparse3(0, D.view(), zd.as<Fr>(), o, o + n, o + 2 * n, nullptr, n, D.chunks.as<LongChunk>(), D.nchunks,
                        D.lrows.as<LongRow>(), D.nlrows, part.as<Fr>(), C.stream);
@@ -3291,7 +3244,8 @@ std::vector<uint8_t> k_eval_on_x(Ctx& C, const HostCsr& m, const uint8_t* r_x) {
     launch_to_mont(rx.as<Fr>(), L + 3, err.as<int>(), C.stream);
     if (D.longc.nchunks > 4096) part.alloc(32 * D.longc.nchunks);
     Fr* o = out.as<Fr>();
-    D.launch(rx.as<Fr>(), L, rx.as<Fr>() + L, o, eqf.as<Fr>(), part.as<Fr>(), C.stream);
+    const ColStreamJob cjob{rx.as<Fr>(), rx.as<Fr>() + L, o, eqf.as<Fr>(), part.as<Fr>()};
+    D.launch(1, &cjob, L, C.stream);
     launch_from_mont(o + n, o, n, C.stream);
     std::vector<uint8_t> res(32 * n);
     SPX_HIP(hipMemcpyAsync(res.data(), o + n, 32 * n, hipMemcpyDeviceToHost, C.stream));
@@ -3329,7 +3283,8 @@ void k_sumcheck_round(Ctx& C, const uint8_t* f, const uint8_t* g, uint64_t n, co
     Fr* Fo = fold ? outs.as<Fr>() : nullptr;
     Fr* Go = fold ? Fo + n / 2 : nullptr;
     Fr* ev = res.as<Fr>();
-    launch_sc2_round(fold, F, Gt, Fo, Go, r, half, part.as<Fr>(), C.ticket, ev, true, C.stream);
+    const Sc2Job rjob{F, Gt, Fo, Go, r, part.as<Fr>(), C.ticket, ev};
+    launch_sc2_round(1, &rjob, fold, true, half, C.stream);
     Fr* canon = ev + 3;
     launch_from_mont(canon, ev, 3, C.stream);
     int herr = 0;

@@ -392,10 +392,10 @@ struct DevColStream {  // rank-local columns of A, B, C for eval_on_x (kernels.h
     ColStreamView view() const {
         return ColStreamView{slices.as<ColSlice>(), lanes.as<uint32_t>(), rowm.as<uint32_t>(), val.as<Fr>(), nslices};
     }
-    // out = sum_m scale[m] M(r_x, .) (eq_scratch: kEqScratch Fr)
-    void launch(const Fr* r_x, int L, const Fr* scale, Fr* out, Fr* eq_scratch, Fr* partial, hipStream_t s) const {
-        launch_col_stream(view(), r_x, L, scale, out, eq_scratch, longc.view(), longc.chunks.as<LongChunk>(),
-                          longc.nchunks, longc.lrows.as<LongRow>(), longc.nlrows, partial, s);
+    // per job: out = sum_m scale[m] M(r_x, .)
+    void launch(int k, const ColStreamJob* jobs, int L, hipStream_t s) const {
+        launch_col_stream(k, jobs, view(), L, longc.view(), longc.chunks.as<LongChunk>(), longc.nchunks,
+                          longc.lrows.as<LongRow>(), longc.nlrows, s);
     }
 };
 struct Index {

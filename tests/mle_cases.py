@@ -12,9 +12,13 @@ Python also does the Montgomery conversion (x 2^256 mod r and back): the kernels
 prepare or decode their own operands. A kernel's output is compared as its 8 x 32-bit Montgomery words
 with the words of the reference value, so a non-canonical representative fails too.
 
-The launch arithmetic of mle_kernels.hip is restated here (grid_for, round_dispatch, open_tail_levels,
-open_eval_plan) so that the shape tables can say, and test_mle_cases.py can assert, which branch each
-shape reaches. All case data comes from seeds; there are no fixture files."""
+The launch arithmetic of mle_kernels.hip is restated here (grid_for, round_dispatch, group_dispatch,
+open_tail_levels, open_eval_plan) so that the shape tables can say, and test_mle_cases.py can assert,
+which branch each shape reaches. The C++ side decides each of these in one function (sc_round_plan,
+open_eval_plan), which every launch goes through, one proof or a group; test_gpu_mle_ops.py compares the
+restatement with those two functions (test_round_plan, test_open_eval_plan). A launcher takes the jobs of k
+proofs: k = 1 is the per-proof launch, k > 1 the group kernels. All case data comes from seeds; there are
+no fixture files."""
 import random
 from functools import lru_cache
 from types import SimpleNamespace
@@ -78,7 +82,7 @@ def grid_for(n, cap=2048):
 
 
 def round_dispatch(which, fold, need1, half):
-    """launch_sc1_round / launch_sc2_round: (form, grid, fused)"""
+    """sc_round_plan (launch_sc1_round / launch_sc2_round): (form, grid, fused)"""
     if half >= WAVE_MIN_HALF:
         g = grid_for(half, WAVE_MAX_BLOCKS)
         return "wave", g, g <= FUSE_MAX_BLOCKS
@@ -96,11 +100,11 @@ def passes(form, grid, n):
     return -(-n // (PER_BLOCK[form] * grid))
 
 
-def group_dispatch(which, fold, need1, half):
-    """launch_sc?_round_group: 'per-proof' (the fallback to the single launcher) or the group kernel's form"""
-    if half < WAVE_MIN_HALF and not (fold and not need1):
-        return "per-proof"
-    return round_dispatch(which, fold, need1, half)[0]
+def group_dispatch(which, fold, need1, half, k):
+    """launch_sc?_round with k jobs: 'per-proof' (the per-proof kernels, one proof after the other: a group
+    of one, and the lane form, which has no group kernel) or the group kernel's form"""
+    form = round_dispatch(which, fold, need1, half)[0]
+    return "per-proof" if k == 1 or form == "lane" else form
 
 
 def open_tail_levels(half, remaining):
@@ -113,7 +117,7 @@ def open_tail_levels(half, remaining):
 
 
 def open_eval_plan(L):
-    """launch_open_eval_group's steps for n = 2^L: ('tail', half, levels) / ('fold', nf, nout, wave) /
+    """open_eval_plan (launch_open_eval's steps) for n = 2^L: ('tail', half, levels) / ('fold', nf, nout, wave) /
     ('level', half), and whether the chain ends on a fold (then a copy writes `last`)"""
     n, i, steps = 1 << L, 0, []
     while i < L:
@@ -132,7 +136,8 @@ def open_eval_plan(L):
 
 
 def tail_launches(k):
-    return [min(TAIL_GROUP, k - j0) for j0 in range(0, k, TAIL_GROUP)]
+    """proofs per k_open_tail_group launch of a group of k > 1 (one proof: k_open_tail itself, no group launch)"""
+    return [min(TAIL_GROUP, k - j0) for j0 in range(0, k, TAIL_GROUP)] if k > 1 else []
 
 
 def spmv_grid(entries, group):

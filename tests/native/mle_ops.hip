@@ -75,14 +75,7 @@ struct Sess {
     }
 };
 
-template <class F>
-void with_bool(bool b, F f) {
-    if (b)
-        f(std::true_type{});
-    else
-        f(std::false_type{});
-}
-#define BV(x) decltype(x)::value
+#define BV(x) SPX_BV(x)  // (with_bool is the launchers' own)
 
 // the argument checks every entry shares: a launch is made only on a valid shape
 bool bad_grid(int mode, int grid) { return mode != 0 && grid < 1; }
@@ -93,10 +86,12 @@ void round_launch(int which, int mode, bool fold, bool need1, bool fused, int gr
     const hipStream_t s = nullptr;
     const int n1 = need1 ? 1 : 0;
     if (mode == 0) {
+        const Sc1Job j1{in, out, Ein, Eout, r, partial, ticket, result3};
+        const Sc2Job j2{in.t[0], in.t[1], out.t[0], out.t[1], r, partial, ticket, result3};
         if (which == 1)
-            launch_sc1_round(fold, in, out, Ein, Eout, r, half, partial, ticket, result3, need1, s);
+            launch_sc1_round(1, &j1, fold, need1, half, s);
         else
-            launch_sc2_round(fold, in.t[0], in.t[1], out.t[0], out.t[1], r, half, partial, ticket, result3, need1, s);
+            launch_sc2_round(1, &j2, fold, need1, half, s);
         return;
     }
     const dim3 g(grid), b(kThreads);
@@ -151,7 +146,7 @@ int guarded(Sess& S, F f) {
 
 // A sumcheck round, launched twice on the same ticket and partials.
 //   which 1: tabs = A, B, C (3 x nin), E (nE);  which 2: tabs = M, Z (2 x nin), E unused
-//   mode 0: launch_sc1_round / launch_sc2_round;  1: k_sc?_round<fold, fused>;  2: k_sc1_fold_quad /
+//   mode 0: launch_sc1_round / launch_sc2_round with one job;  1: k_sc?_round<fold, fused>;  2: k_sc1_fold_quad /
 //   k_sc2_fold_pair<fused>;  3: k_sc?_wave<fold, need1, fused>. Direct unfused launches are followed by
 //   k_reduce_partials<3> over `grid` blocks.
 //   in/out: out (ntab x nout), Eout (nEout; null: no E output), partial (npartial), result6 (the pattern
@@ -190,8 +185,8 @@ MLE_API int mle_round(int which, int mode, int fold, int need1, int fused, int g
     });
 }
 
-// The same round for the k jobs of a lockstep group through launch_sc1_round_group /
-// launch_sc2_round_group, twice. Per job j: its tables at tabs + j ntab nin, E at E + j nE, challenge
+// The same round for the k jobs of a lockstep group through launch_sc1_round / launch_sc2_round,
+// twice. Per job j: its tables at tabs + j ntab nin, E at E + j nE, challenge
 // r[j], outputs at out + j ntab nout, Eout + j nEout, partials at partial + j npartial;
 // result (2 x k x 3, the pattern in the first 3 Fr): launch i's result3 of job j at (i k + j) 3;
 // ticket2: 2 x k words.
@@ -232,9 +227,9 @@ MLE_API int mle_round_group(int which, int k, int fold, int need1, const Fr* tab
             S.reup(dres, pat.data(), 3 * k);
             if (!S.good()) break;
             if (which == 1)
-                launch_sc1_round_group(k, fold, j1.data(), half, need1, nullptr);
+                launch_sc1_round(k, j1.data(), fold, need1, half, nullptr);
             else
-                launch_sc2_round_group(k, fold, j2.data(), half, need1, nullptr);
+                launch_sc2_round(k, j2.data(), fold, need1, half, nullptr);
             if (!S.sync()) break;
             S.down(result + (uint64_t)3 * k * rep, dres, 3 * k);
             S.down(ticket2 + k * rep, dtick, k);
@@ -259,7 +254,7 @@ MLE_API int mle_reduce_partials(const Fr* partial, int nblk, Fr* out3) {
     });
 }
 
-// eq tables. k == 0: launch_eq_table; k >= 1: launch_eq_table_group for k proofs (r: k x nvar, out:
+// eq tables. k == 0: launch_eq_table with one job; k >= 1: with the jobs of k proofs (r: k x nvar, out:
 // k x count, in/out). The scratch tables hold 2^13 entries each, per proof.
 MLE_API int mle_eq_table(int k, const Fr* r, int nvar, uint64_t base, uint64_t count, Fr* out) {
     Sess S;
@@ -271,16 +266,11 @@ MLE_API int mle_eq_table(int k, const Fr* r, int nvar, uint64_t base, uint64_t c
         Fr* dlo = S.scratch<Fr>((uint64_t)kk << 13);
         Fr* dhi = S.scratch<Fr>((uint64_t)kk << 13);
         if (!S.good()) return;
-        if (k == 0) {
-            launch_eq_table(dr, nvar, base, count, dout, dlo, dhi, nullptr);
-        } else {
-            std::vector<const Fr*> rs(k);
-            std::vector<Fr*> os(k), los(k), his(k);
-            for (int j = 0; j < k; ++j)
-                rs[j] = dr + (uint64_t)j * nvar, os[j] = dout + (uint64_t)j * count, los[j] = dlo + ((uint64_t)j << 13),
-                his[j] = dhi + ((uint64_t)j << 13);
-            launch_eq_table_group(k, rs.data(), nvar, base, count, os.data(), los.data(), his.data(), nullptr);
-        }
+        std::vector<EqTableJob> jobs(kk);
+        for (int j = 0; j < kk; ++j)
+            jobs[j] = EqTableJob{dr + (uint64_t)j * nvar, dout + (uint64_t)j * count, dlo + ((uint64_t)j << 13),
+                                 dhi + ((uint64_t)j << 13)};
+        launch_eq_table(kk, jobs.data(), nvar, base, count, nullptr);
         S.sync();
         S.down(out, dout, (uint64_t)kk * count);
     });
@@ -401,7 +391,30 @@ MLE_API int mle_open_tail(const Fr* rin, uint64_t half, int nlev, const Fr* poin
 
 MLE_API int mle_open_tail_levels(uint64_t half, int remaining) { return open_tail_levels(half, remaining); }
 
-// launch_open_eval_group: z (k x n, n = 2^L), points (k x L, host side as the launcher takes them),
+// The launch plans, host arithmetic only (no launch). sc_round_plan: out4 = form (kRoundLane / kRoundSplit /
+// kRoundWave), grid, fused, per-proof
+MLE_API int mle_round_plan(int which, int k, int fold, int need1, uint64_t half, int* out4) {
+    if ((which != 1 && which != 2) || k < 1 || k > kGroupMax || half < 1 || !out4) return -1;
+    const RoundPlan p = sc_round_plan(which, k, fold, need1, half);
+    out4[0] = p.form, out4[1] = p.grid, out4[2] = p.fused, out4[3] = p.per_proof;
+    return 0;
+}
+// open_eval_plan(L): per step 5 words (kind kOpenTail / kOpenFold / kOpenLevel, first level, levels, size,
+// wave) into steps (room for `cap` steps), *copy = the chain ends on a fold; returns the number of steps
+MLE_API int mle_open_eval_plan(int L, uint64_t* steps, int cap, int* copy) {
+    if (L < 1 || L > 26 || !steps || !copy) return -1;
+    const OpenEvalPlan pl = open_eval_plan(L);
+    if ((int)pl.steps.size() > cap) return -1;
+    for (size_t i = 0; i < pl.steps.size(); ++i) {
+        const OpenStep& st = pl.steps[i];
+        uint64_t* w = steps + 5 * i;
+        w[0] = st.kind, w[1] = st.first, w[2] = st.levels, w[3] = st.size, w[4] = st.wave;
+    }
+    *copy = pl.copy;
+    return (int)pl.steps.size();
+}
+
+// launch_open_eval with k jobs: z (k x n, n = 2^L), points (k x L, host side as the launcher takes them),
 // last (k, in/out); bufA / bufB are n/2 and n/4 Fr per proof
 MLE_API int mle_open_eval_group(int k, const Fr* z, const Fr* points, int L, Fr* last) {
     Sess S;
@@ -413,25 +426,26 @@ MLE_API int mle_open_eval_group(int k, const Fr* z, const Fr* points, int L, Fr*
         Fr* dB = S.scratch<Fr>((uint64_t)k * (n / 4));
         Fr* dl = S.up(last, k);
         if (!S.good()) return;
-        std::vector<const Fr*> zs(k);
-        std::vector<Fr*> As(k), Bs(k), ls(k);
+        std::vector<OpenEvalJob> jobs(k);
         for (int j = 0; j < k; ++j)
-            zs[j] = dz + (uint64_t)j * n, As[j] = dA + (uint64_t)j * (n / 2), Bs[j] = dB ? dB + (uint64_t)j * (n / 4) : nullptr,
-            ls[j] = dl + j;
-        launch_open_eval_group(k, zs.data(), As.data(), Bs.data(), points, L, n, ls.data(), nullptr);
+            jobs[j] = OpenEvalJob{dz + (uint64_t)j * n, dA + (uint64_t)j * (n / 2), dB ? dB + (uint64_t)j * (n / 4) : nullptr,
+                                  points + (uint64_t)j * L, dl + j};
+        launch_open_eval(k, jobs.data(), L, nullptr);
         S.sync();
         S.down(last, dl, k);
     });
 }
 
-// the sliced SpMV. k == 0: launch_spmv_sliced; k >= 1: launch_spmv_sliced_group. val / col / dst:
-// `entries` each (dst = row | matrix << 30, row < nrows, col < nz); z: k x nz; out: per proof Az, Bz, Cz
-// (3 x nrows), in/out
-MLE_API int mle_spmv(int k, const Fr* val, const uint32_t* col, const uint32_t* dst, uint64_t entries, const Fr* z,
-                     uint64_t nz, Fr* out, uint64_t nrows) {
+// the sliced SpMV. mle_spmv: launch_spmv_sliced with one job (k == 0) or the jobs of k >= 1 proofs (a
+// group of one is the per-proof kernel too). mle_spmv_group_direct: k_spmv_sliced_group itself for k >= 1
+// proofs with `grid` blocks (a multiple of 8). val / col / dst: `entries` each (dst = row | matrix << 30,
+// row < nrows, col < nz); z: k x nz; out: per proof Az, Bz, Cz (3 x nrows), in/out
+static int spmv_entry(int k, const Fr* val, const uint32_t* col, const uint32_t* dst, uint64_t entries, const Fr* z,
+                      uint64_t nz, Fr* out, uint64_t nrows, int grid) {
     Sess S;
     const int kk = k < 1 ? 1 : k;
     if (k < 0 || k > kGroupMax || entries < 1 || !val || !col || !dst || !z || !out) return -1;
+    if (grid < 0 || grid % 8 || (grid && k < 1)) return -1;
     for (uint64_t e = 0; e < entries; ++e)
         if (col[e] >= nz || (dst[e] >> 30) > 2 || (dst[e] & 0x3FFFFFFFu) >= nrows) return -1;
     return guarded(S, [&] {
@@ -440,20 +454,26 @@ MLE_API int mle_spmv(int k, const Fr* val, const uint32_t* col, const uint32_t* 
         Fr* dz = S.up(z, (uint64_t)kk * nz);
         Fr* dout = S.up(out, (uint64_t)kk * 3 * nrows);
         if (!S.good()) return;
-        if (k == 0) {
-            launch_spmv_sliced(v, dz, dout, dout + nrows, dout + 2 * nrows, entries, nullptr);
-        } else {
-            std::vector<const Fr*> zs(k);
-            std::vector<Tables3> os(k);
-            for (int j = 0; j < k; ++j) {
-                zs[j] = dz + (uint64_t)j * nz;
-                for (int m = 0; m < 3; ++m) os[j].t[m] = dout + ((uint64_t)j * 3 + m) * nrows;
-            }
-            launch_spmv_sliced_group(k, v, zs.data(), os.data(), entries, nullptr);
+        GroupOf<SpmvJob> g{};
+        for (int j = 0; j < kk; ++j) {
+            g.j[j].z = dz + (uint64_t)j * nz;
+            for (int m = 0; m < 3; ++m) g.j[j].o[m] = dout + ((uint64_t)j * 3 + m) * nrows;
         }
+        if (grid == 0)
+            launch_spmv_sliced(kk, g.j, v, entries, nullptr);
+        else
+            hipLaunchKernelGGL(k_spmv_sliced_group, dim3(grid), dim3(kThreads), 0, nullptr, v, g, k, entries);
         S.sync();
         S.down(out, dout, (uint64_t)kk * 3 * nrows);
     });
+}
+MLE_API int mle_spmv(int k, const Fr* val, const uint32_t* col, const uint32_t* dst, uint64_t entries, const Fr* z,
+                     uint64_t nz, Fr* out, uint64_t nrows) {
+    return spmv_entry(k, val, col, dst, entries, z, nz, out, nrows, 0);
+}
+MLE_API int mle_spmv_group_direct(int k, int grid, const Fr* val, const uint32_t* col, const uint32_t* dst,
+                                  uint64_t entries, const Fr* z, uint64_t nz, Fr* out, uint64_t nrows) {
+    return grid < 1 ? -1 : spmv_entry(k, val, col, dst, entries, z, nz, out, nrows, grid);
 }
 
 // conversions over n elements. mode 0: launch_to_mont in place (err: out, the kernel's flag word);
@@ -478,7 +498,7 @@ MLE_API int mle_mont(int mode, int grid, Fr* data, uint64_t n, int* err) {
     });
 }
 
-// launch_copy_runs_group: per proof j, nruns runs of `per` Fr (src: k x nruns x per) -> dst + j nruns per
+// launch_copy_runs: per proof j, nruns runs of `per` Fr (src: k x nruns x per) -> dst + j nruns per
 // (dst: k x nruns x per, in/out)
 MLE_API int mle_copy_runs(int k, const Fr* src, int nruns, int per, Fr* dst) {
     Sess S;
@@ -488,14 +508,12 @@ MLE_API int mle_copy_runs(int k, const Fr* src, int nruns, int per, Fr* dst) {
         Fr* ds = S.up(src, k * np);
         Fr* dd = S.up(dst, k * np);
         if (!S.good()) return;
-        std::vector<Tables3> srcs(k);
-        std::vector<Fr*> dsts(k);
+        std::vector<CopyJob> jobs(k);
         for (int j = 0; j < k; ++j) {
-            srcs[j] = Tables3{};
-            for (int i = 0; i < nruns; ++i) srcs[j].t[i] = ds + j * np + (uint64_t)i * per;
-            dsts[j] = dd + j * np;
+            jobs[j] = CopyJob{{nullptr, nullptr, nullptr}, dd + j * np};
+            for (int i = 0; i < nruns; ++i) jobs[j].src[i] = ds + j * np + (uint64_t)i * per;
         }
-        launch_copy_runs_group(k, srcs.data(), nruns, per, dsts.data(), nullptr);
+        launch_copy_runs(k, jobs.data(), nruns, per, nullptr);
         S.sync();
         S.down(dst, dd, k * np);
     });

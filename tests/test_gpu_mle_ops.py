@@ -46,6 +46,9 @@ def lib():
         "mle_open_tail_levels": [c_u64, c_int],
         "mle_open_eval_group": [c_int, vp, vp, c_int, vp],
         "mle_spmv": [c_int, vp, vp, vp, c_u64, vp, c_u64, vp, c_u64],
+        "mle_spmv_group_direct": [c_int, c_int, vp, vp, vp, c_u64, vp, c_u64, vp, c_u64],
+        "mle_round_plan": [c_int, c_int, c_int, c_int, c_u64, vp],
+        "mle_open_eval_plan": [c_int, vp, c_int, vp],
         "mle_mont": [c_int, c_int, vp, c_u64, vp],
         "mle_copy_runs": [c_int, vp, c_int, c_int, vp],
     }
@@ -189,10 +192,10 @@ def _group_id(p):
 @pytest.mark.parametrize("p", mc.GROUP_ROUNDS, ids=_group_id)
 @pytest.mark.parametrize("which", [1, 2])
 def test_round_group(lib, which, p):
-    """launch_sc1_round_group / launch_sc2_round_group: distinct tables and challenges per job, every
+    """launch_sc1_round / launch_sc2_round with k jobs: distinct tables and challenges per job, every
     job's outputs equal the reference of its own tables"""
     k, half, fold, need1 = p
-    form = mc.group_dispatch(which, fold, need1, half)
+    form = mc.group_dispatch(which, fold, need1, half, k)
     _, grid, fused = mc.round_dispatch(which, fold, need1, half)
     jobs = [mc.build_round(which, half, fold, "rand", seed=100 + j) for j in range(k)]
     c0 = jobs[0]
@@ -252,7 +255,7 @@ def test_eq_table_window(lib, win, kind):
 
 @pytest.mark.parametrize("shape", [(3, 0, 8), (14, 0, 1 << 14), (25, (1 << 25) - 300, 300)], ids=lambda s: "nvar%d-count%d" % (s[0], s[2]))
 def test_eq_table_group(lib, shape):
-    """launch_eq_table_group with k = 3 distinct points"""
+    """launch_eq_table with the jobs of k = 3 distinct points"""
     nvar, base, count = shape
     rs = [mc.eq_point(nvar, "rand", seed=j) for j in range(3)]
     got = run_eq_table(lib, 3, rs, nvar, base, count)
@@ -389,11 +392,58 @@ def test_open_tail_levels(lib, hrl):
     assert lib.mle_open_tail_levels(half, remaining) == want == mc.open_tail_levels(half, remaining)
 
 
+def _plan_rounds():
+    """every (which, fold, need1, half) of the round case tables, and the halves around the wave threshold"""
+    out = {(w, f, n1, h) for w, h, f, n1, _ in mc.launcher_round_params()}
+    out |= {(w, f, n1, h) for w, h, f, n1, _ in mc.edge_round_params()}
+    out |= {(w, f, n1, h) for _, h, f, n1 in mc.GROUP_ROUNDS for w in (1, 2)}
+    out |= {(w, f, n1, h) for w in (1, 2) for f in (0, 1) for n1 in (0, 1)
+            for h in (1 << 13, (1 << 14) - 1, 1 << 14, 1 << 16, 1 << 20)}
+    return sorted(out)
+
+
+def test_round_plan(lib):
+    """sc_round_plan, the one place of mle_kernels.hip that decides a round's form, grid, fused-or-reduce and
+    per-proof launching, against round_dispatch / group_dispatch (host arithmetic, no launch)"""
+    forms = {0: ("lane", "lane"), 1: ("quad", "pair"), 2: ("wave", "wave")}  # kRoundLane, kRoundSplit, kRoundWave
+    for which, fold, need1, half in _plan_rounds():
+        for k in (1, 2, 3, mc.GROUP_MAX):
+            got = np.full(4, -1, dtype=np.int32)
+            assert lib.mle_round_plan(which, k, fold, need1, half, ptr(got)) == 0
+            form, grid, fused = mc.round_dispatch(which, fold, need1, half)
+            what = (which, k, fold, need1, half)
+            assert (forms[int(got[0])][which - 1], int(got[1]), bool(got[2])) == (form, grid, fused), what
+            assert bool(got[3]) == (mc.group_dispatch(which, fold, need1, half, k) == "per-proof"), what
+
+
+@pytest.mark.parametrize("Lv", sorted(set(mc.OPEN_EVAL_L) | {1, 2, 10, 11, 20}))
+def test_open_eval_plan(lib, Lv):
+    """open_eval_plan, the stubbed opening chain's steps for one proof and for a group, against
+    mc.open_eval_plan (host arithmetic, no launch)"""
+    steps = np.zeros((32, 5), dtype=np.uint64)
+    copy = np.full(1, -1, dtype=np.int32)
+    n = lib.mle_open_eval_plan(Lv, ptr(steps), 32, ptr(copy))
+    want, want_copy = mc.open_eval_plan(Lv)
+    assert n == len(want) and bool(copy[0]) == want_copy
+    first = 0
+    for (kind, at, levels, size, wave), w in zip(steps[:n].tolist(), want):
+        assert at == first
+        if w[0] == "tail":    # kOpenTail
+            assert (kind, size, levels, wave) == (0, w[1], w[2], 0)
+        elif w[0] == "fold":  # kOpenFold
+            assert (kind, levels, size, bool(wave)) == (1, w[1], w[2], w[3])
+        else:                 # kOpenLevel
+            assert (kind, levels, size, wave) == (2, 1, w[1], 0)
+        first += levels
+    assert first == Lv
+
+
 @pytest.mark.parametrize("k", mc.OPEN_EVAL_K)
 @pytest.mark.parametrize("Lv", mc.OPEN_EVAL_L)
 def test_open_eval_group(lib, Lv, k):
-    """launch_open_eval_group: last[j] = z_j(point_j) by the oracle's mle_eval (L = 17 goes through the wave
-    group fold, k = 9 through two tail launches)"""
+    """launch_open_eval with k jobs: last[j] = z_j(point_j) by the oracle's mle_eval. k = 1 walks the chain
+    with the per-proof launchers (L = 1 ends on a level, whose output the copy kernel moves to `last`); k = 8
+    and 9 take the group kernels (L = 17 the wave group fold, k = 9 two tail launches)"""
     n = 1 << Lv
     zs = [mc.open_table(n, "rand", seed=1000 + j) for j in range(k)]
     ps = [mc.open_points(Lv, "edges" if j == 1 and Lv >= 3 else "rand", seed=j) for j in range(k)]
@@ -433,13 +483,19 @@ def test_spmv_sliced(lib, entries):
 @pytest.mark.parametrize("entries", [9, 8 * 1024 + 1])
 @pytest.mark.parametrize("k", mc.SPMV_GROUP_K)
 def test_spmv_sliced_group(lib, k, entries):
-    """launch_spmv_sliced_group: k = 1 and 3 end its two-at-a-time loop on an odd proof"""
+    """k_spmv_sliced_group: k = 1 and 3 end its two-at-a-time loop on an odd proof. k = 2, 3 through
+    launch_spmv_sliced; a group of one is the per-proof kernel there, so k = 1 launches the group kernel
+    itself, at the launcher's group grid"""
     c = mc.spmv_case(entries)
     zs = [mc.spmv_z(c.nz, j) for j in range(k)]
     val_w, z_w = mc.mont_words(c.val), mc.mont_words([v for z in zs for v in z])
     col, dst = np.array(c.col, dtype=np.uint32), np.array(c.dst, dtype=np.uint32)
     out = mc.pattern(k * 3 * c.nrows)
-    call(lib, "mle_spmv", k, ptr(val_w), ptr(col), ptr(dst), entries, ptr(z_w), c.nz, ptr(out), c.nrows)
+    args = (ptr(val_w), ptr(col), ptr(dst), entries, ptr(z_w), c.nz, ptr(out), c.nrows)
+    if k == 1:
+        call(lib, "mle_spmv_group_direct", k, mc.spmv_grid(entries, True), *args)
+    else:
+        call(lib, "mle_spmv", k, *args)
     check_spmv(c, zs, out)
 
 
@@ -477,7 +533,7 @@ def test_from_mont_round_trip(lib):
 
 @pytest.mark.parametrize("shape", [(1, 1, 1), (3, 3, 5), (16, 2, 700), (2, 1, 4096)], ids=lambda s: "k%d-runs%d-per%d" % s)
 def test_copy_runs_group(lib, shape):
-    """launch_copy_runs_group: the runs of each proof back to back, words unchanged"""
+    """launch_copy_runs: the runs of each proof back to back, words unchanged"""
     k, nruns, per = shape
     src = np.arange(k * nruns * per * 8, dtype=np.uint32).reshape(-1, 8)
     dst = mc.pattern(k * nruns * per)

@@ -178,12 +178,18 @@ def test_edge_and_group_shapes_reach_their_branches():
     for k, half, fold, need1 in mc.GROUP_ROUNDS:
         assert 1 <= k <= mc.GROUP_MAX and (k < 16 or half <= 1 << 14)
         for which in (1, 2):
-            forms.setdefault(mc.group_dispatch(which, fold, need1, half), set()).add(k)
+            forms.setdefault(mc.group_dispatch(which, fold, need1, half, k), set()).add(k)
             _, g, fused = mc.round_dispatch(which, fold, need1, half)
             if half == 1 << 15:
                 assert not fused, "k_reduce_partials_group"
-    assert forms["wave"] >= {1, 3, 16} and forms["per-proof"] >= {1, 3, 16}
-    assert forms["quad"] >= {1, 3, 16} and forms["pair"] >= {1, 3, 16}
+    # a group of one is the per-proof launch whatever its shape; the lane form is per-proof at every k
+    assert forms["wave"] == {3, 16} and forms["quad"] == {3, 16} and forms["pair"] == {3, 16}
+    assert forms["per-proof"] == {1, 3, 16}
+    for which in (1, 2):
+        one = {mc.round_dispatch(which, f, n1, h)[0] for k, h, f, n1 in mc.GROUP_ROUNDS if k == 1}
+        assert one == {"wave", "quad" if which == 1 else "pair", "lane"}, "k = 1 rows of every form, all per-proof"
+        for kk in (3, 16):
+            assert any(mc.group_dispatch(which, f, n1, h, k) == "per-proof" for k, h, f, n1 in mc.GROUP_ROUNDS if k == kk)
     assert {k for k, *_ in mc.GROUP_ROUNDS} == {1, 3, 16}
 
 
@@ -227,7 +233,8 @@ def test_opening_shapes_reach_their_branches():
     # no group chain reaches the 2-level fold: two remaining levels always fit the tail
     for L in range(1, 27):
         assert all(s[:2] != ("fold", 2) for s in mc.open_eval_plan(L)[0])
-    assert [mc.tail_launches(k) for k in mc.OPEN_EVAL_K] == [[1], [8], [8, 1]]
+    # one proof takes k_open_tail itself; 8 proofs fill one group tail launch, 9 need a second
+    assert [mc.tail_launches(k) for k in mc.OPEN_EVAL_K] == [[], [8], [8, 1]]
 
 
 def test_eq_and_spmv_shapes_reach_their_branches():
