@@ -6,8 +6,10 @@
  *
  * Byte conventions (ark-serialize, the reference's own wire format):
  *   Fr        32-byte little-endian canonical integer (`into_repr` bytes)
- *   G1 / G2   96 / 192-byte UNCOMPRESSED affine points (public-parameter files),
- *             48 / 96-byte COMPRESSED points inside proofs
+ *   G1 / G2   96 / 192-byte UNCOMPRESSED affine points (spx_pp_load / spx_pp_serialize, every
+ *             VerifierParameter argument), 48 / 96-byte COMPRESSED points inside proofs and in the
+ *             compressed public-parameter form (spx_pp_load_compressed / spx_pp_serialize_compressed;
+ *             spx_vp_convert takes a VerifierParameter from one form to the other)
  *   Matrix    CSR: row_ptr[n+1] (u64), col[nnz] (u32), val[nnz] (Fr bytes); the row order and
  *             the order of entries inside a row are the `ark_relations::r1cs::Matrix<F>` order
  *             (they are hashed into the Fiat-Shamir transcript, /root/reference/src/lib.rs:61-64).
@@ -16,7 +18,12 @@
  *   spx_index            MLArgumentForR1CS::index                 src/lib.rs:45-51 -> src/ahp/indexer.rs:41-64
  *   spx_prove            MLArgumentForR1CS::prove                 src/lib.rs:58-146
  *   spx_verify           MLArgumentForR1CS::verify                src/lib.rs:147-212
- *   spx_pp_load          PublicParameter (CanonicalDeserialize)   src/commitment/data_structures.rs:9-17
+ *   spx_pp_load          PublicParameter::deserialize_unchecked of serialize_uncompressed bytes  src/commitment/data_structures.rs:9-17
+ *   spx_pp_serialize     PublicParameter::serialize_uncompressed
+ *   spx_pp_load_compressed       PublicParameter::deserialize (CanonicalDeserialize's default, compressed;
+ *                                with spx_pp_check_subgroup: the checked deserialize)
+ *   spx_pp_serialize_compressed  PublicParameter::serialize (CanonicalSerialize's default, compressed)
+ *   spx_vp_convert       VerifierParameter::serialize <-> serialize_uncompressed bytes
  *   spx_pp_generate      MLProofForR1CS::setup / MLPolyCommit::keygen  src/ahp/setup.rs:13-16, src/commitment/setup.rs:27-105
  *   spx_commit           MLPolyCommit::commit                     src/commitment/commit.rs:17-29
  *   spx_open             MLPolyCommit::open                       src/commitment/open.rs:19-58
@@ -163,6 +170,30 @@ int spx_ctx_mem_info(spx_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 int spx_pp_load(spx_ctx *ctx, const uint8_t *bytes, size_t len, spx_pp **out);
 int spx_pp_generate(spx_ctx *ctx, int nv, uint64_t seed, spx_pp **out);
 int spx_pp_serialize(spx_pp *pp, uint8_t *out, size_t cap, size_t *len);
+/* The compressed wire form: what `pp.serialize(&mut w)` writes and `PublicParameter::deserialize` reads
+ * (ark-serialize's default methods). The framing is that of the uncompressed form in the derive order of
+ * data_structures.rs:9-17 (u64 nv, u64 nv, per G1 level u64 2^(nv-i) and its points, u64 nv, per G2 level
+ * likewise, g, h) with 48-byte G1 and 96-byte G2 points: half the bytes to store and to move over PCIe.
+ *
+ * spx_pp_load_compressed: the points are decompressed on the GPU straight into the parameter's device
+ * layout, with the acceptance of spx_g1_decompress / spx_g2_decompress; then the handle is preprocessed as
+ * spx_pp_load's and cannot be told apart from one (views, derived VP, checks, window plans, memory).
+ * Framing errors give spx_pp_load's messages. A rejected point gives SPX_SERIALIZATION naming the lowest
+ * offender in the order of spx_pp_check_subgroup (G1 levels, G2 levels, g, h), e.g.
+ * "powers_of_h level 2 point 5: x is not canonical" or "...: no point on the curve with this x".
+ * The bytes are uploaded through a device staging buffer in chunks of at most 2^SPX_PP_STAGE_LOG points
+ * (environment, read at each call; default 20: at most 96 MiB of staging whatever the size).
+ * spx_pp_serialize_compressed: the contract of spx_pp_serialize (len receives the size; SPX_INVALID_ARGUMENT
+ * if cap is too small) for loaded and generated parameters and views, staged in the same chunks.
+ * spx_pp_serialized_size: the byte length of an nv-variable parameter (1..26) in either form; host only. */
+int spx_pp_load_compressed(spx_ctx *ctx, const uint8_t *bytes, size_t len, spx_pp **out);
+int spx_pp_serialize_compressed(spx_pp *pp, uint8_t *out, size_t cap, size_t *len);
+int spx_pp_serialized_size(int nv, int compressed, size_t *len);
+/* A VerifierParameter (u64 nv, g, h, u64 count, g_mask_random) from the uncompressed form, which
+ * spx_verify / spx_verify_many / spx_pc_verify take, to the compressed one (to_compressed = 1) or back
+ * (0), on the host: a Rust host passes `vp.serialize()` through this call first. Malformed input
+ * (truncated, trailing bytes, a non-canonical x, an x with no point) gives SPX_SERIALIZATION. */
+int spx_vp_convert(const uint8_t *in, size_t in_len, int to_compressed, uint8_t *out, size_t cap, size_t *len);
 int spx_pp_free(spx_pp *pp);
 
 /* ---- index / witness / prove ---- */
@@ -412,6 +443,14 @@ int spx_msm_g2(spx_ctx *ctx, const uint8_t *bases, const uint8_t *scalars, size_
  * a non-canonical x or an x with no point on the curve (its output bytes are zero). */
 int spx_g1_decompress(spx_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out_uncompressed, uint8_t *ok);
 int spx_g2_decompress(spx_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out_uncompressed, uint8_t *ok);
+/* the compressed public-parameter loader's and serializer's kernels. _decompress_bulk: the contract of
+ * spx_g1_decompress / spx_g2_decompress through the loader's throughput kernels. _compress: n uncompressed
+ * points (canonical; infinity by the ark flag) to 48 / 96 compressed bytes each. After any of these six
+ * calls the first entry of spx_last_timings is the device time of the conversion kernel alone. */
+int spx_g1_decompress_bulk(spx_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out_uncompressed, uint8_t *ok);
+int spx_g2_decompress_bulk(spx_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out_uncompressed, uint8_t *ok);
+int spx_g1_compress(spx_ctx *ctx, const uint8_t *in_uncompressed, size_t n, uint8_t *out_compressed);
+int spx_g2_compress(spx_ctx *ctx, const uint8_t *in_uncompressed, size_t n, uint8_t *out_compressed);
 /* out[s] = sum_{seg_off[s] <= i < seg_off[s + 1]} scalar_i base_i for n uncompressed bases and n canonical
  * Fr scalars; seg_off: nseg + 1 ascending offsets from 0 to n. Infinity carries the ark flag in both
  * directions. */

@@ -170,6 +170,14 @@ EXPORTED = [
     "spx_pp_check_structure",
     "spx_pp_view",
     "spx_pp_mem_info",
+    "spx_pp_load_compressed",
+    "spx_pp_serialize_compressed",
+    "spx_pp_serialized_size",
+    "spx_vp_convert",
+    "spx_g1_decompress_bulk",
+    "spx_g2_decompress_bulk",
+    "spx_g1_compress",
+    "spx_g2_compress",
 ]
 
 _lib = None
@@ -311,6 +319,15 @@ def lib():
         L.spx_pp_check_structure.argtypes = [vp, vp, u8p, pu64, pu64, ctypes.POINTER(ctypes.c_int)]
         L.spx_pp_view.argtypes = [vp, vp, ctypes.c_int, ctypes.POINTER(vp)]
         L.spx_pp_mem_info.argtypes = [vp, pu64]
+    if hasattr(L, "spx_pp_load_compressed") or not os.environ.get("SPX_LIB_PATH"):  # A/B builds may predate it
+        L.spx_pp_load_compressed.argtypes = [vp, u8p, sz, ctypes.POINTER(vp)]
+        L.spx_pp_serialize_compressed.argtypes = [vp, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
+        L.spx_pp_serialized_size.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(sz)]
+        L.spx_vp_convert.argtypes = [u8p, sz, ctypes.c_int, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
+        L.spx_g1_decompress_bulk.argtypes = [vp, u8p, sz, ctypes.c_void_p, ctypes.c_void_p]
+        L.spx_g2_decompress_bulk.argtypes = [vp, u8p, sz, ctypes.c_void_p, ctypes.c_void_p]
+        L.spx_g1_compress.argtypes = [vp, u8p, sz, ctypes.c_void_p]
+        L.spx_g2_compress.argtypes = [vp, u8p, sz, ctypes.c_void_p]
     for name in EXPORTED:
         if name not in ("spx_last_error", "spx_version", "spx_proof_size"):
             if os.environ.get("SPX_LIB_PATH") and not hasattr(L, name):
@@ -676,6 +693,20 @@ class PublicParameter:
             pp.check_structure()
         return pp
 
+    @staticmethod
+    def load_compressed(ctx, data, check_subgroup=False, check_structure=False):
+        """load() for the compressed wire form, what arkworks' `pp.serialize()` writes (48 / 96-byte points,
+        decompressed on the GPU; spx_pp_load_compressed). With check_subgroup=True this is arkworks' checked
+        `PublicParameter::deserialize`. A rejected point raises SerializationError naming the lowest one."""
+        h = ctypes.c_void_p()
+        _check(lib().spx_pp_load_compressed(ctx.h, bytes(data), len(data), ctypes.byref(h)))
+        pp = PublicParameter(ctx, h, int.from_bytes(data[:8], "little"))
+        if check_subgroup:
+            pp.check_subgroup()
+        if check_structure:
+            pp.check_structure()
+        return pp
+
     def view(self, nv, ctx=None):
         """The public parameter of nv <= self.nv variables that this one contains (spx_pp_view): it borrows
         this parameter's device storage and builds only its own commitment table. Either handle may be
@@ -745,6 +776,14 @@ class PublicParameter:
         buf = ctypes.create_string_buffer(n.value)
         _check(lib().spx_pp_serialize(self.h, buf, n.value, ctypes.byref(n)))
         return buf.raw
+
+    def serialize_compressed(self):
+        """The compressed wire form, the bytes of arkworks' `pp.serialize()` (spx_pp_serialize_compressed)"""
+        cap = serialized_size(self.nv, True)
+        buf = ctypes.create_string_buffer(cap)
+        n = ctypes.c_size_t(0)
+        _check(lib().spx_pp_serialize_compressed(self.h, buf, cap, ctypes.byref(n)))
+        return buf.raw[: n.value]
 
     def __del__(self):
         try:
@@ -1125,6 +1164,25 @@ def verifier_parameter(pp):
     return out.raw[: n.value]
 
 
+def serialized_size(nv, compressed):
+    """Byte length of an nv-variable PublicParameter in the compressed or the uncompressed wire form
+    (spx_pp_serialized_size; no GPU)"""
+    n = ctypes.c_size_t(0)
+    _check(lib().spx_pp_serialized_size(int(nv), 1 if compressed else 0, ctypes.byref(n)))
+    return n.value
+
+
+def vp_convert(data, to_compressed):
+    """VerifierParameter bytes in the other wire form (spx_vp_convert; no GPU): to_compressed=False turns
+    arkworks' `vp.serialize()` into what verify / verify_many / MLPolyCommit.verify take"""
+    data = bytes(data)
+    cap = 2 * len(data) + 16
+    out = ctypes.create_string_buffer(cap)
+    n = ctypes.c_size_t(0)
+    _check(lib().spx_vp_convert(data, len(data), 1 if to_compressed else 0, out, cap, ctypes.byref(n)))
+    return out.raw[: n.value]
+
+
 def _many_args(vs, proofs):
     k = len(proofs)
     if k != len(vs):
@@ -1181,6 +1239,35 @@ def g1_decompress(ctx, compressed):
 
 def g2_decompress(ctx, compressed):
     return _decompress(lib().spx_g2_decompress, ctx, compressed, 96)
+
+
+def g1_decompress_bulk(ctx, compressed):
+    """g1_decompress through the compressed public-parameter loader's kernel (spx_g1_decompress_bulk)"""
+    return _decompress(lib().spx_g1_decompress_bulk, ctx, compressed, 48)
+
+
+def g2_decompress_bulk(ctx, compressed):
+    return _decompress(lib().spx_g2_decompress_bulk, ctx, compressed, 96)
+
+
+def _compress(fn, ctx, data, ps):
+    data = bytes(data)
+    if not data or len(data) % ps:
+        raise InvalidArgument("uncompressed points are %d bytes each" % ps)
+    n = len(data) // ps
+    out = ctypes.create_string_buffer(ps // 2 * n)
+    _check(fn(ctx.h, data, n, out))
+    return out.raw
+
+
+def g1_compress(ctx, uncompressed):
+    """compressed bytes of concatenated 96-byte uncompressed G1 points, by the compressed public-parameter
+    serializer's kernel (spx_g1_compress)"""
+    return _compress(lib().spx_g1_compress, ctx, uncompressed, 96)
+
+
+def g2_compress(ctx, uncompressed):
+    return _compress(lib().spx_g2_compress, ctx, uncompressed, 192)
 
 
 # One launch of the membership kernels covers this many points; a longer array takes a second pass of

@@ -307,6 +307,34 @@ int spx_pp_serialize(spx_pp* pp, uint8_t* out, size_t cap, size_t* len) {
         copy_out(spx::pp_serialize(*pp->ctx->c, *pp->p), out, cap, len);
     });
 }
+int spx_pp_load_compressed(spx_ctx* ctx, const uint8_t* bytes, size_t len, spx_pp** out) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (!bytes || !out) spx::invalid("null argument");
+        set_dev(ctx);
+        auto* p = new spx_pp{ctx, spx::pp_load_compressed(*ctx->c, bytes, len)};
+        *out = p;
+    });
+}
+int spx_pp_serialize_compressed(spx_pp* pp, uint8_t* out, size_t cap, size_t* len) {
+    return guard([&] {
+        if (!pp) spx::invalid("null public parameter");
+        set_dev(pp->ctx);
+        copy_out(spx::pp_serialize_compressed(*pp->ctx->c, *pp->p), out, cap, len);
+    });
+}
+int spx_pp_serialized_size(int nv, int compressed, size_t* len) {
+    return guard([&] {
+        if (!len) spx::invalid("null argument");
+        *len = spx::pp_serialized_size(nv, compressed != 0);
+    });
+}
+int spx_vp_convert(const uint8_t* in, size_t in_len, int to_compressed, uint8_t* out, size_t cap, size_t* len) {
+    return guard([&] {
+        if (!in) spx::invalid("null argument");
+        copy_out(spx::vp_convert(in, in_len, to_compressed != 0), out, cap, len);
+    });
+}
 int spx_pp_window_plan(spx_pp* pp, int level, int* c, int* windows) {
     return guard([&] {
         if (!pp || !c || !windows) spx::invalid("null argument");
@@ -929,6 +957,42 @@ int spx_g2_decompress(spx_ctx* ctx, const uint8_t* in, size_t n, uint8_t* out_un
         set_dev(ctx);
         spx::CtxClaim claim(*ctx->c);
         spx::k_decompress(*ctx->c, true, in, n, out_uncompressed, ok);
+    });
+}
+int spx_g1_decompress_bulk(spx_ctx* ctx, const uint8_t* in, size_t n, uint8_t* out_uncompressed, uint8_t* ok) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (!in || !out_uncompressed || !ok) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_decompress(*ctx->c, false, in, n, out_uncompressed, ok, true);
+    });
+}
+int spx_g2_decompress_bulk(spx_ctx* ctx, const uint8_t* in, size_t n, uint8_t* out_uncompressed, uint8_t* ok) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (!in || !out_uncompressed || !ok) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_decompress(*ctx->c, true, in, n, out_uncompressed, ok, true);
+    });
+}
+int spx_g1_compress(spx_ctx* ctx, const uint8_t* in_uncompressed, size_t n, uint8_t* out_compressed) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (!in_uncompressed || !out_compressed) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_compress(*ctx->c, false, in_uncompressed, n, out_compressed);
+    });
+}
+int spx_g2_compress(spx_ctx* ctx, const uint8_t* in_uncompressed, size_t n, uint8_t* out_compressed) {
+    return guard([&] {
+        if (!ctx) spx::invalid("null context");
+        if (!in_uncompressed || !out_compressed) spx::invalid("null argument");
+        set_dev(ctx);
+        spx::CtxClaim claim(*ctx->c);
+        spx::k_compress(*ctx->c, true, in_uncompressed, n, out_compressed);
     });
 }
 int spx_lincomb_g1(spx_ctx* ctx, const uint8_t* bases_uncompressed, const uint8_t* scalars, size_t n,

@@ -472,4 +472,21 @@ static constexpr uint32_t kPPSumThreads = 256, kPPSumMaxBlocks = 256;
 uint32_t odd_sum_blocks(int nv);
 void launch_odd_sum_g1(const G1Aff* pts, int nv, G1Xyzz* part, G1Xyzz* out, hipStream_t s);
 
+// ---- pp_codec_kernels.hip ("Compressed public parameters")
+// n ark-serialize compressed points (`in` 16-byte aligned) -> out[0 .. n), affine Montgomery, (0, 0) for
+// infinity and for a rejected point, with the acceptance of launch_decompress_g1 / _g2. Every rejected
+// point j lowers *err (initialised to kCodecNoError) to ((point_base + j) << 2) | reason by one atomic
+// minimum: afterwards it names the lowest rejected point. ok: one byte per point as launch_decompress_*,
+// or null (the loader wants only the report).
+static constexpr unsigned long long kCodecNoError = ~0ull;
+static constexpr uint32_t kCodecNotCanonical = 1, kCodecNoPoint = 2;  // reasons
+void launch_decompress_bulk_g1(const uint8_t* in, uint64_t n, G1Aff* out, uint64_t point_base, unsigned long long* err,
+                               uint8_t* ok, hipStream_t s);
+void launch_decompress_bulk_g2(const uint8_t* in, uint64_t n, G2Aff* out, uint64_t point_base, unsigned long long* err,
+                               uint8_t* ok, hipStream_t s);
+// n affine Montgomery points -> 48 / 96 compressed bytes each (`out` 16-byte aligned), the bytes of
+// host::g1_compress / g2_compress
+void launch_compress_g1(const G1Aff* in, uint64_t n, uint8_t* out, hipStream_t s);
+void launch_compress_g2(const G2Aff* in, uint64_t n, uint8_t* out, hipStream_t s);
+
 }  // namespace spx

@@ -456,6 +456,175 @@ std::vector<uint8_t> pp_serialize(Ctx& C, const PP& P) {
     return out;
 }
 
+// ---- the compressed wire form ("Compressed public parameters"): what ark-serialize's
+// serialize() / deserialize() write and read. The framing is the uncompressed form's with 48 / 96-byte
+// points; the bulk conversion runs on the GPU (pp_codec_kernels.hip) and only compressed bytes cross PCIe.
+size_t pp_serialized_size(int nv, bool compressed) {
+    if (nv < 1 || nv > kMaxLogN) invalid("nv out of range (1..26 supported)");
+    const size_t g1 = compressed ? 48 : 96, pts = (2ull << nv) - 2;
+    return 24 + 16 * (size_t)nv + 3 * g1 * pts + 3 * g1;
+}
+// SPX_PP_STAGE_LOG: log2 of the points per staging chunk of the compressed loader and serializer (default
+// 20: a staging buffer of at most 96 MiB, whatever the parameter's size). Read at each call.
+static constexpr int kPPStageLogDefault = 20;
+static uint64_t pp_stage_points() {
+    const char* e = getenv("SPX_PP_STAGE_LOG");
+    long v = kPPStageLogDefault;
+    if (e && *e) {
+        char* end = nullptr;
+        const long t = strtol(e, &end, 10);
+        if (end != e && *end == 0) v = std::min(std::max(t, 0l), 27l);  // anything but a number: the default
+    }
+    return 1ull << v;
+}
+// The 2 tot points of a parameter in the order G1 levels, G2 levels, cut into chunks of at most `chunk`
+// points; a chunk is at most one run of G1 points followed by one run of G2 points. fn(first G1 point,
+// G1 points, first G2 point, G2 points).
+template <class Fn>
+static void pp_for_chunks(uint64_t tot, uint64_t chunk, const Fn& fn) {
+    for (uint64_t c0 = 0; c0 < 2 * tot; c0 += chunk) {
+        const uint64_t c1 = std::min(c0 + chunk, 2 * tot);
+        const uint64_t a0 = std::min(c0, tot), a1 = std::min(c1, tot);
+        const uint64_t b0 = std::max(c0, tot) - tot, b1 = std::max(c1, tot) - tot;
+        fn(a0, a1 - a0, b0, b1 - b0);
+    }
+}
+// Points [p0, p0 + cnt) of one curve, level by level: fn(level, first point within the level, points,
+// points of the run before this piece)
+template <class Fn>
+static void pp_for_level_pieces(const std::vector<uint64_t>& lvl_off, int nv, uint64_t p0, uint64_t cnt, const Fn& fn) {
+    uint64_t done = 0;
+    for (int i = 0; i < nv && done < cnt; ++i) {
+        const uint64_t lo = std::max(p0 + done, lvl_off[i]), hi = std::min(p0 + cnt, lvl_off[i + 1]);
+        if (lo >= hi) continue;
+        fn(i, lo - lvl_off[i], hi - lo, done);
+        done += hi - lo;
+    }
+}
+// 0: host::g1_decompress / g2_decompress accepts the bytes; else the kernels' reason (kernels.hpp)
+static uint32_t point_reject_reason(const uint8_t* p, bool g2) {
+    host::Fq t;
+    if (!host::fq_from_bytes(t, p, nullptr) || (g2 && !host::fq_from_bytes(t, p + 48, nullptr))) return kCodecNotCanonical;
+    if (g2) {
+        host::Affine<host::Fq2> a;
+        return host::g2_decompress(a, p) ? 0 : kCodecNoPoint;
+    }
+    host::Affine<host::Fq> a;
+    return host::g1_decompress(a, p) ? 0 : kCodecNoPoint;
+}
+static const char* codec_reason(uint32_t r) {
+    return r == kCodecNotCanonical ? "x is not canonical" : "no point on the curve with this x";
+}
+
+std::unique_ptr<PP> pp_load_compressed(Ctx& C, const uint8_t* b, size_t len) {
+    auto P = std::make_unique<PP>();
+    size_t pos = 0;
+    auto need = [&](size_t k) {
+        if (pos + k > len) throw SpxError(kSerialization, "truncated public parameter bytes");
+    };
+    auto u64 = [&]() {
+        need(8);
+        uint64_t v;
+        memcpy(&v, b + pos, 8);
+        pos += 8;
+        return v;
+    };
+    uint64_t nv = u64();
+    if (nv < 1 || nv > (uint64_t)kMaxLogN) throw SpxError(kSerialization, "bad public parameter nv (1..26 supported)");
+    if (u64() != nv) throw SpxError(kSerialization, "powers_of_g length != nv");
+    std::vector<size_t> g1_pos(nv), g2_pos(nv);
+    for (uint64_t i = 0; i < nv; ++i) {
+        if (u64() != (1ull << (nv - i))) throw SpxError(kSerialization, "powers_of_g level size");
+        need(48ull << (nv - i));
+        g1_pos[i] = pos;
+        pos += 48ull << (nv - i);
+    }
+    if (u64() != nv) throw SpxError(kSerialization, "powers_of_h length != nv");
+    for (uint64_t i = 0; i < nv; ++i) {
+        if (u64() != (1ull << (nv - i))) throw SpxError(kSerialization, "powers_of_h level size");
+        need(96ull << (nv - i));
+        g2_pos[i] = pos;
+        pos += 96ull << (nv - i);
+    }
+    need(48 + 96);
+    pp_alloc_raw(*P, (int)nv, C.device);
+    const uint64_t tot = P->lvl_off[nv], chunk = pp_stage_points();
+    DevMem stage(96 * std::min(chunk, 2 * tot)), err(sizeof(unsigned long long));
+    const unsigned long long none = kCodecNoError;
+    unsigned long long herr = none;
+    SPX_HIP(hipMemcpyAsync(err.p, &none, sizeof(none), hipMemcpyHostToDevice, C.stream));
+    uint8_t* const st = stage.as<uint8_t>();
+    pp_for_chunks(tot, chunk, [&](uint64_t a0, uint64_t na, uint64_t b0, uint64_t nb) {
+        pp_for_level_pieces(P->lvl_off, (int)nv, a0, na, [&](int i, uint64_t first, uint64_t cnt, uint64_t before) {
+            SPX_HIP(hipMemcpyAsync(st + 48 * before, b + g1_pos[i] + 48 * first, 48 * cnt, hipMemcpyHostToDevice, C.stream));
+        });
+        pp_for_level_pieces(P->lvl_off, (int)nv, b0, nb, [&](int i, uint64_t first, uint64_t cnt, uint64_t before) {
+            SPX_HIP(hipMemcpyAsync(st + 48 * na + 96 * before, b + g2_pos[i] + 96 * first, 96 * cnt, hipMemcpyHostToDevice,
+                                   C.stream));
+        });
+        launch_decompress_bulk_g1(st, na, P->g1_raw() + a0, a0, err.as<unsigned long long>(), nullptr, C.stream);
+        launch_decompress_bulk_g2(st + 48 * na, nb, P->g2_raw() + b0, tot + b0, err.as<unsigned long long>(), nullptr,
+                                  C.stream);
+    });
+    SPX_HIP(hipMemcpyAsync(&herr, err.p, sizeof(herr), hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    // the lowest offender in the order G1 levels, G2 levels, g, h
+    if (herr != none) {
+        const uint64_t pt = herr >> 2;
+        const bool g2 = pt >= tot;
+        const uint64_t idx = g2 ? pt - tot : pt;
+        int lvl = 0;
+        while (idx >= P->lvl_off[lvl + 1]) ++lvl;
+        throw SpxError(kSerialization, std::string(g2 ? "powers_of_h" : "powers_of_g") + " level " + std::to_string(lvl) +
+                                           " point " + std::to_string(idx - P->lvl_off[lvl]) + ": " +
+                                           codec_reason((uint32_t)(herr & 3)));
+    }
+    if (const uint32_t r = point_reject_reason(b + pos, false)) throw SpxError(kSerialization, std::string("g: ") + codec_reason(r));
+    if (const uint32_t r = point_reject_reason(b + pos + 48, true)) throw SpxError(kSerialization, std::string("h: ") + codec_reason(r));
+    host::g1_decompress(P->g, b + pos);
+    host::g2_decompress(P->h, b + pos + 48);
+    pp_preprocess(C, *P);
+    return P;
+}
+
+std::vector<uint8_t> pp_serialize_compressed(Ctx& C, const PP& P) {
+    const int nv = P.nv;
+    const uint64_t tot = P.lvl_off[nv], chunk = pp_stage_points();
+    std::vector<uint8_t> out(pp_serialized_size(nv, true));
+    // the framing first: where each level's points go
+    std::vector<size_t> g1_pos(nv), g2_pos(nv);
+    uint8_t* p = out.data();
+    const uint64_t u = (uint64_t)nv;
+    memcpy(p, &u, 8), p += 8;
+    for (int c = 0; c < 2; ++c) {
+        memcpy(p, &u, 8), p += 8;
+        for (int i = 0; i < nv; ++i) {
+            const uint64_t k = 1ull << (nv - i);
+            memcpy(p, &k, 8), p += 8;
+            (c ? g2_pos : g1_pos)[i] = (size_t)(p - out.data());
+            p += (c ? 96 : 48) * k;
+        }
+    }
+    host::g1_compress(p, P.g), p += 48;
+    host::g2_compress(p, P.h), p += 96;
+    DevMem stage(96 * std::min(chunk, 2 * tot));
+    uint8_t* const st = stage.as<uint8_t>();
+    pp_for_chunks(tot, chunk, [&](uint64_t a0, uint64_t na, uint64_t b0, uint64_t nb) {
+        launch_compress_g1(P.g1_raw() + a0, na, st, C.stream);
+        launch_compress_g2(P.g2_raw() + b0, nb, st + 48 * na, C.stream);
+        pp_for_level_pieces(P.lvl_off, nv, a0, na, [&](int i, uint64_t first, uint64_t cnt, uint64_t before) {
+            SPX_HIP(hipMemcpyAsync(out.data() + g1_pos[i] + 48 * first, st + 48 * before, 48 * cnt, hipMemcpyDeviceToHost,
+                                   C.stream));
+        });
+        pp_for_level_pieces(P.lvl_off, nv, b0, nb, [&](int i, uint64_t first, uint64_t cnt, uint64_t before) {
+            SPX_HIP(hipMemcpyAsync(out.data() + g2_pos[i] + 96 * first, st + 48 * na + 96 * before, 96 * cnt,
+                                   hipMemcpyDeviceToHost, C.stream));
+        });
+    });
+    C.sync();
+    return out;
+}
+
 // ====================================================================== index
 static void check_csr(const HostCsr& m, uint64_t n) {
     if (m.n != n) invalid("matrix size is inconsistent with number of constraints");
@@ -2860,21 +3029,37 @@ void verify_many(Ctx& C, Index& I, const uint8_t* const* v, const size_t* nv, co
 }
 
 // ---- kernel-level entries of the batch verifier's kernels (parity tests)
-void k_decompress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok) {
+void k_decompress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok, bool bulk) {
     if (n == 0) invalid("no points");
     const size_t cs = g2 ? 96 : 48, ps = 2 * cs;
     DevMem din(cs * n), pts(ps * n), dok(n);
+    EventPair ev;  // the decompression kernel alone, for spx_last_timings
     SPX_HIP(hipMemcpyAsync(din.p, in, cs * n, hipMemcpyHostToDevice, C.stream));
-    if (g2) {
+    DevMem err(sizeof(unsigned long long));  // the loader's report (bulk kernels); this entry answers per point
+    SPX_HIP(hipMemsetAsync(err.p, 0xff, sizeof(unsigned long long), C.stream));
+    SPX_HIP(hipEventRecord(ev.a, C.stream));
+    if (bulk) {
+        if (g2)
+            launch_decompress_bulk_g2(din.as<uint8_t>(), n, pts.as<G2Aff>(), 0, err.as<unsigned long long>(),
+                                      dok.as<uint8_t>(), C.stream);
+        else
+            launch_decompress_bulk_g1(din.as<uint8_t>(), n, pts.as<G1Aff>(), 0, err.as<unsigned long long>(),
+                                      dok.as<uint8_t>(), C.stream);
+    } else if (g2) {
         launch_decompress_g2(din.as<uint8_t>(), n, pts.as<G2Aff>(), dok.as<uint8_t>(), C.stream);
-        launch_points_to_canon_g2(pts.as<G2Aff>(), n, C.stream);
     } else {
         launch_decompress_g1(din.as<uint8_t>(), n, pts.as<G1Aff>(), dok.as<uint8_t>(), C.stream);
-        launch_points_to_canon_g1(pts.as<G1Aff>(), n, C.stream);
     }
+    SPX_HIP(hipEventRecord(ev.b, C.stream));
+    if (g2)
+        launch_points_to_canon_g2(pts.as<G2Aff>(), n, C.stream);
+    else
+        launch_points_to_canon_g1(pts.as<G1Aff>(), n, C.stream);
     SPX_HIP(hipMemcpyAsync(out, pts.p, ps * n, hipMemcpyDeviceToHost, C.stream));
     SPX_HIP(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, C.stream));
     C.sync();
+    C.timings.clear();
+    C.timings.emplace_back(bulk ? "decompress_bulk_kernel" : "decompress_kernel", 1000.0 * ev.ms());
     for (size_t j = 0; j < n; ++j) {  // infinity carries the ark flag; a rejected point stays all zero
         uint8_t* p = out + ps * j;
         bool zero = true;
@@ -2884,6 +3069,84 @@ void k_decompress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out, ui
             p[ps - 1] |= host::kFlagInf;
         }
     }
+}
+// n uncompressed ark points -> compressed bytes through the serializer's kernel
+void k_compress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out) {
+    if (n == 0) invalid("no points");
+    const size_t cs = g2 ? 96 : 48, ps = 2 * cs;
+    DevMem pts(ps * n), dout(cs * n), err(sizeof(int));
+    EventPair ev;
+    SPX_HIP(hipMemsetAsync(err.p, 0, sizeof(int), C.stream));
+    SPX_HIP(hipMemcpyAsync(pts.p, in, ps * n, hipMemcpyHostToDevice, C.stream));
+    if (g2)
+        launch_points_from_bytes_g2(pts.as<G2Aff>(), n, err.as<int>(), C.stream);
+    else
+        launch_points_from_bytes_g1(pts.as<G1Aff>(), n, err.as<int>(), C.stream);
+    SPX_HIP(hipEventRecord(ev.a, C.stream));
+    if (g2)
+        launch_compress_g2(pts.as<G2Aff>(), n, dout.as<uint8_t>(), C.stream);
+    else
+        launch_compress_g1(pts.as<G1Aff>(), n, dout.as<uint8_t>(), C.stream);
+    SPX_HIP(hipEventRecord(ev.b, C.stream));
+    int herr = 0;
+    SPX_HIP(hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, C.stream));
+    SPX_HIP(hipMemcpyAsync(out, dout.p, cs * n, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    if (herr & 1) throw SpxError(kSerialization, "non-canonical coordinate");
+    if (herr & 2) throw SpxError(kSerialization, "point not on the curve");
+    C.timings.clear();
+    C.timings.emplace_back("compress_kernel", 1000.0 * ev.ms());
+}
+// A VerifierParameter between the two wire forms (nv, g, h, u64 count, g_mask_random), on the host
+std::vector<uint8_t> vp_convert(const uint8_t* b, size_t len, bool to_compressed) {
+    const size_t g1_in = to_compressed ? 96 : 48;
+    size_t pos = 0;
+    auto take = [&](size_t k) {
+        if (k > len - pos) throw SpxError(kSerialization, "truncated verifier parameter");
+        const uint8_t* p = b + pos;
+        pos += k;
+        return p;
+    };
+    Ser s;
+    uint8_t buf[192];
+    auto g1 = [&](const char* what) {
+        const uint8_t* p = take(g1_in);
+        host::Affine<host::Fq> a;
+        if (to_compressed) {
+            if (!host::g1_from_uncompressed(a, p)) throw SpxError(kSerialization, std::string("bad ") + what);
+            host::g1_compress(buf, a);
+        } else {
+            if (const uint32_t r = point_reject_reason(p, false))
+                throw SpxError(kSerialization, std::string(what) + ": " + codec_reason(r));
+            host::g1_decompress(a, p);
+            host::g1_to_uncompressed(buf, a);
+        }
+        s.raw(buf, to_compressed ? 48 : 96);
+    };
+    uint64_t nv, cnt;
+    memcpy(&nv, take(8), 8);
+    if (nv > (uint64_t)kMaxLogN) throw SpxError(kSerialization, "bad verifier parameter nv (<= 26 supported)");
+    s.u64(nv);
+    g1("g");
+    {
+        const uint8_t* p = take(2 * g1_in);
+        host::Affine<host::Fq2> a;
+        if (to_compressed) {
+            if (!host::g2_from_uncompressed(a, p)) throw SpxError(kSerialization, "bad h");
+            host::g2_compress(buf, a);
+        } else {
+            if (const uint32_t r = point_reject_reason(p, true)) throw SpxError(kSerialization, std::string("h: ") + codec_reason(r));
+            host::g2_decompress(a, p);
+            host::g2_to_uncompressed(buf, a);
+        }
+        s.raw(buf, to_compressed ? 96 : 192);
+    }
+    memcpy(&cnt, take(8), 8);
+    if (cnt != nv) throw SpxError(kSerialization, "g_mask_random length != nv");
+    s.u64(cnt);
+    for (uint64_t i = 0; i < cnt; ++i) g1("g_mask_random point");
+    if (pos != len) throw SpxError(kSerialization, "trailing bytes in verifier parameter");
+    return s.b;
 }
 void k_lincomb(Ctx& C, bool g2, const uint8_t* bases, const uint8_t* scalars, size_t n, const uint64_t* seg_off,
                size_t nseg, uint8_t* out) {

@@ -453,6 +453,11 @@ void host_phase_stats(uint64_t* out);
 std::unique_ptr<PP> pp_load(Ctx& C, const uint8_t* b, size_t len);
 std::unique_ptr<PP> pp_generate(Ctx& C, int nv, uint64_t seed);
 std::vector<uint8_t> pp_serialize(Ctx& C, const PP& P);
+// the compressed wire form (ark-serialize's serialize() / deserialize()): 48 / 96-byte points, converted on
+// the GPU in staging chunks of 2^SPX_PP_STAGE_LOG points
+std::unique_ptr<PP> pp_load_compressed(Ctx& C, const uint8_t* b, size_t len);
+std::vector<uint8_t> pp_serialize_compressed(Ctx& C, const PP& P);
+size_t pp_serialized_size(int nv, bool compressed);
 std::unique_ptr<Index> index_build(Ctx& C, const HostCsr* mats);
 // diagnostic (spx_index_export): the raw bytes of device array `part` (spartan_hip.h: SPX_IDX_*) of an index,
 // logical length (empty for a part the index does not have)
@@ -492,6 +497,8 @@ struct VP {
 };
 VP vp_load(const uint8_t* b, size_t len);
 std::vector<uint8_t> vp_serialize(const VP& V);
+// the bytes of a VerifierParameter in the other wire form (host only)
+std::vector<uint8_t> vp_convert(const uint8_t* b, size_t len, bool to_compressed);
 VP vp_from_pp(const PP& P);  // keygen-generated PP only (keeps the trapdoor)
 // The verifier parameter of any PP: g_mask[i] = the sum of the odd-index points of powers_of_g[i] (= g^{t_i}
 // for a parameter with the structure pp_check_structure tests), summed on the GPU (pp_kernels.hip)
@@ -532,7 +539,11 @@ std::vector<uint8_t> verify_many_coeffs(const uint8_t* const* v, const size_t* n
                                         const size_t* lens, int k, const uint8_t* vp, size_t vp_len,
                                         const uint8_t* entropy32);
 // n compressed points -> uncompressed ark bytes (infinity flagged; all zero where ok[j] = 0)
-void k_decompress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok);
+// bulk: through the compressed loader's kernels (pp_codec_kernels.hip) instead of the batch verifier's.
+// spx_last_timings then holds the decompression kernel's device time alone.
+void k_decompress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok, bool bulk = false);
+// n uncompressed ark points (canonical, on no curve check) -> compressed bytes by the serializer's kernels
+void k_compress(Ctx& C, bool g2, const uint8_t* in, size_t n, uint8_t* out);
 // out[s] = sum over segment s of scalar_i base_i; uncompressed ark bytes in and out
 void k_lincomb(Ctx& C, bool g2, const uint8_t* bases, const uint8_t* scalars, size_t n, const uint64_t* seg_off,
                size_t nseg, uint8_t* out);
